@@ -10,6 +10,13 @@ labels, 8 inner epochs of minibatch SGD on CBF+actor, polyak target update.
 value = environment transitions processed per second across the WHOLE JOB
 (n_env * 256 * steps / elapsed summed over ranks); config.train_steps_per_sec
 carries the per-step rate for BASELINE.md's table.
+
+A plain run only sets up, warms up, times ``--steps`` training steps and prints
+the JSON result line. ``--dump-outputs DIR`` additionally writes what the last
+timed step returned (metrics, rollout, updated parameters) as ``DIR/*.npy`` so
+two builds can be compared output for output. ``--full`` is the switch for any
+measurement beyond the headline figure; the benchmark currently has none, so it
+changes nothing yet.
 """
 import argparse
 import json
@@ -28,6 +35,41 @@ from gcbfplus_amd.trainer.utils import collect_rollout
 # fast CI smoke of the JSON contract, never for reported numbers
 N_ENV_PER_GPU = int(os.environ.get("GCBF_BENCH_ENVS", 16))
 T_HORIZON = int(os.environ.get("GCBF_BENCH_T", 256))
+# --dump-outputs writes at most this many float32 elements in all (60 MB)
+DUMP_BUDGET_ELEMS = 15_000_000
+
+
+def dump_outputs(out_dir, algo, rollout, info):
+    """Write what the last timed training step handed back: its metric dict,
+    the rollout it collected and the parameters it left behind. float32 for
+    tensors, float64 for the host-side metrics; ~30 MB at the default config.
+    Past DUMP_BUDGET_ELEMS in total (large --num-agents) every array over its
+    equal share is cut to a fixed seeded sample of its flattened elements."""
+    os.makedirs(out_dir, exist_ok=True)
+    keys = sorted(info)
+    np.save(os.path.join(out_dir, "info.npy"),
+            np.array([info[k] for k in keys], dtype=np.float64))
+    with open(os.path.join(out_dir, "info_keys.txt"), "w") as f:
+        f.write("\n".join(keys) + "\n")
+
+    arrays = {}
+    for name in ("states", "masks", "actions", "rewards", "costs", "dones",
+                 "next_states", "next_mask"):
+        arrays["rollout_" + name] = getattr(rollout, name)
+    for name in ("cbf", "cbf_tgt", "actor"):
+        net = getattr(algo, name, None)
+        if net is not None:
+            arrays["params_" + name] = torch.cat(
+                [p.reshape(-1) for p in net.parameters()])
+    cap = None
+    if sum(t.numel() for t in arrays.values()) > DUMP_BUDGET_ELEMS:
+        cap = DUMP_BUDGET_ELEMS // len(arrays)
+    for name, t in arrays.items():
+        a = t.detach().to(torch.float32).cpu().numpy()
+        if cap is not None and a.size > cap:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, cap, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def main():
@@ -40,6 +82,12 @@ def main():
     ap.add_argument("--torch-profile", type=str, default=None, metavar="TRACE.json",
                     help="wrap the timed steps in torch.profiler and export a "
                          "chrome trace (SURVEY.md §5.1 observability)")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's outputs "
+                         "(metrics, rollout, updated parameters) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run measurements beyond the headline figure "
+                         "(none exist yet; a plain run stays lean)")
     args = ap.parse_args()
 
     local_rank = dp.setup_from_env()
@@ -67,10 +115,14 @@ def main():
 
         graphed = GraphedRolloutStep(env, algo.step)
 
+    last = {}
+
     def train_step(step):
         graph0 = env.reset(N_ENV_PER_GPU, rng)
         rollout = collect_rollout(env, algo.step, graph0, graphed)
-        return algo.update(rollout, step)
+        info = algo.update(rollout, step)
+        last["rollout"], last["info"] = rollout, info
+        return info
 
     for i in range(args.warmup):
         train_step(i)
@@ -106,6 +158,9 @@ def main():
         t = torch.tensor([elapsed], device=device if use_cuda else "cpu")
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    if args.dump_outputs and dp.rank() == 0 and last:
+        dump_outputs(args.dump_outputs, algo, last["rollout"], last["info"])
 
     if dp.rank() == 0:
         steps_per_sec = args.steps / elapsed

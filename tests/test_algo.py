@@ -327,6 +327,46 @@ def test_bench_contract_json(tmp_path):
     assert d["data"] == "synthetic" and d["higher_is_better"] is True
 
 
+def test_bench_dump_outputs(tmp_path):
+    """bench.py --dump-outputs writes the last timed step's metrics, rollout
+    and parameters as float32/float64 .npy files; --full is accepted and
+    --steps sets the number of timed steps."""
+    import json
+    import subprocess
+    import sys
+
+    env_vars = dict(os.environ, GCBF_BENCH_ENVS="2", GCBF_BENCH_T="16")
+    dump = tmp_path / "dump"
+    out = subprocess.run(
+        [sys.executable, "bench.py", "--cpu", "--gpus", "1", "--steps", "2",
+         "--warmup", "0", "--num-agents", "2", "--full",
+         "--dump-outputs", str(dump)],
+        capture_output=True, text=True, timeout=900, env=env_vars,
+        cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+    )
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = json.loads([l for l in out.stdout.strip().splitlines() if l.startswith("{")][-1])
+    assert d["steps"] == 2 and d["ms_per_step"] > 0
+    assert abs(d["config"]["train_steps_per_sec"] * d["ms_per_step"] - 1000.0) < 1e-6
+
+    files = sorted(p.name for p in dump.glob("*.npy"))
+    for name in ("info.npy", "rollout_states.npy", "rollout_actions.npy",
+                 "params_cbf.npy", "params_actor.npy"):
+        assert name in files, (name, files)
+    total = 0
+    for f in files:
+        a = np.load(dump / f)
+        assert a.dtype in (np.float32, np.float64), (f, a.dtype)
+        assert np.isfinite(a).all(), f
+        total += a.nbytes
+    assert total <= 64 * 2**20
+    keys = (dump / "info_keys.txt").read_text().split()
+    assert len(keys) == np.load(dump / "info.npy").shape[0] > 0
+    # 2 envs x 16 steps x (2 agents + 2 goals + 2*32 rays) nodes x 4 state dims
+    assert np.load(dump / "rollout_states.npy").shape[:2] == (2, 16)
+    assert np.load(dump / "rollout_actions.npy").shape == (2, 16, 2, 2)
+
+
 def test_tanh_distribution_normalizes():
     """log_prob of the tanh-squashed Normal integrates to ~1 over [-1, 1]
     (interior density + the two tail point-masses at +-threshold)."""

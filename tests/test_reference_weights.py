@@ -1,6 +1,7 @@
 """Behavioral parity anchor: load the REFERENCE's own pretrained pickles
-(/root/reference/pretrained/<Env>/gcbf+/models/1000/{actor,cbf}.pkl, written
-by reference gcbf.py:344-349) into this framework's nets and check the
+(<Env>/gcbf+/models/1000/{actor,cbf}.pkl as written by reference
+gcbf.py:344-349, stored byte-for-byte under tests/golden/reference_pretrained)
+into this framework's nets and check the
 policy actually works — this exercises the jax-free unpickler, the flax-tree
 layout mapping, and the full forward stack (edges, GNN, u_ref, dynamics,
 masks) end-to-end against weights trained in the reference implementation.
@@ -16,32 +17,49 @@ from gcbfplus_amd.algo.utils import load_flax_pickle
 from gcbfplus_amd.env import make_env
 from gcbfplus_amd.trainer.utils import collect_rollout
 
-REF = "/root/reference/pretrained"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="reference not present")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden",
+                      "reference_pretrained")
 
 
-def _algo_with_ref_weights(env_id, n_agents, area_size, device="cpu", **env_kw):
+@pytest.fixture(scope="module")
+def ref_dir(tmp_path_factory):
+    """The checkpoints in the reference's directory layout. Each ~1.4 MB
+    pickle is stored as two halves (.part0 + .part1) to keep every committed
+    file under 1 MiB; joining them restores the original bytes."""
+    root = tmp_path_factory.mktemp("reference_pretrained")
+    for env_id in sorted(os.listdir(GOLDEN)):
+        out = root / env_id / "gcbf+" / "models" / "1000"
+        out.mkdir(parents=True)
+        for net in ("actor", "cbf"):
+            with open(out / f"{net}.pkl", "wb") as f:
+                for part in ("part0", "part1"):
+                    with open(os.path.join(GOLDEN, env_id, f"{net}.pkl.{part}"), "rb") as g:
+                        f.write(g.read())
+    return str(root)
+
+
+def _algo_with_ref_weights(ref_dir, env_id, n_agents, area_size, device="cpu", **env_kw):
     env = make_env(env_id, n_agents, area_size=area_size, device=device, **env_kw)
     algo = make_algo(algo="gcbf+", env=env, node_dim=env.node_dim,
                      edge_dim=env.edge_dim, state_dim=env.state_dim,
                      action_dim=env.action_dim, n_agents=n_agents)
-    algo.load(os.path.join(REF, env_id, "gcbf+", "models"), 1000)
+    algo.load(os.path.join(ref_dir, env_id, "gcbf+", "models"), 1000)
     return env, algo
 
 
-def test_load_flax_pickle_no_jax():
-    tree = load_flax_pickle(os.path.join(REF, "DoubleIntegrator/gcbf+/models/1000/cbf.pkl"))
+def test_load_flax_pickle_no_jax(ref_dir):
+    tree = load_flax_pickle(os.path.join(ref_dir, "DoubleIntegrator/gcbf+/models/1000/cbf.pkl"))
     p = tree["params"]
     assert set(p) == {"GNN_0", "CBFHead", "Dense_0"}
     k = p["GNN_0"]["GNNLayer_0"]["msg"]["Dense_0"]["kernel"]
     assert isinstance(k, np.ndarray) and k.dtype == np.float32 and k.ndim == 2
 
 
-def test_reference_di_weights_drive_safely():
+def test_reference_di_weights_drive_safely(ref_dir):
     """Reference DI checkpoint in this framework: zero collisions and most
     agents reach goals within one episode (reference claims high safe/reach
     at n=8; measured here 100%/94% over 4 epi — see BASELINE.md)."""
-    env, algo = _algo_with_ref_weights("DoubleIntegrator", 8, 4.0)
+    env, algo = _algo_with_ref_weights(ref_dir, "DoubleIntegrator", 8, 4.0)
     rng = np.random.default_rng(1234)
     g = env.reset(1, rng)
     ro = collect_rollout(env, algo.act, g)
@@ -55,10 +73,10 @@ def test_reference_di_weights_drive_safely():
     assert finish.mean().item() >= 0.5, "most agents should reach their goals"
 
 
-def test_reference_weights_h_sign_sanity():
+def test_reference_weights_h_sign_sanity(ref_dir):
     """h from the reference CBF weights: positive at a spread-out reset,
     negative when two agents are forced into collision."""
-    env, algo = _algo_with_ref_weights("DoubleIntegrator", 8, 4.0)
+    env, algo = _algo_with_ref_weights(ref_dir, "DoubleIntegrator", 8, 4.0)
     rng = np.random.default_rng(7)
     g = env.reset(1, rng)
     h0 = algo.get_cbf(g)
@@ -80,11 +98,11 @@ def test_reference_weights_h_sign_sanity():
     ("LinearDrone", 8, 4.0),
     ("CrazyFlie", 8, 4.0),
 ])
-def test_reference_weights_load_all_envs(env_id, n, area):
+def test_reference_weights_load_all_envs(ref_dir, env_id, n, area):
     """Every reference pretrained checkpoint loads and produces finite,
     sane outputs through this framework's forward stack (full behavioral
     evals recorded in profiles/ref_*_eval*.log / BASELINE.md)."""
-    env, algo = _algo_with_ref_weights(env_id, n, area)
+    env, algo = _algo_with_ref_weights(ref_dir, env_id, n, area)
     rng = np.random.default_rng(5)
     g = env.reset(1, rng)
     h = algo.get_cbf(g)
