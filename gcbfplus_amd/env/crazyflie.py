@@ -13,12 +13,14 @@ python-`control` ct.lqr, :488-536).
 from __future__ import annotations
 
 import math
+import os
 from typing import Optional, Tuple
 
 import numpy as np
 import torch
 from torch import Tensor
 
+from .. import ops
 from ..utils.graph import GraphBatch
 from .base import StepResult
 from .linear_drone import LinearDrone
@@ -27,6 +29,8 @@ from .utils import sample_starts_goals
 
 # state indices (reference :58)
 X, Y, Z, PSI, THETA, PHI, U, V, W, R_, Q_, P_ = range(12)
+
+GRAVITY = 9.81
 
 
 def rotmat(phi: Tensor, theta: Tensor, psi: Tensor) -> Tensor:
@@ -117,7 +121,7 @@ class CrazyFlie(LinearDrone):
     @property
     def u_eq(self) -> torch.Tensor:
         """Hover: total (CT-normalized) thrust = m g (reference :538-548)."""
-        u = torch.full((4,), self._params["m"] * 9.81 / 4)
+        u = torch.full((4,), self._params["m"] * GRAVITY / 4)
         if not self.normalize_by_CT:
             u = u / self._params["CT"]
         return u
@@ -158,7 +162,7 @@ class CrazyFlie(LinearDrone):
             torch.stack([one, s_phi * t_th, c_phi * t_th], -1),
         ], dim=-2)
         deuler = torch.einsum("...ij,...j->...i", mat, pqr)
-        acc_g = -Rm[..., 2, :] * 9.81  # body-frame gravity
+        acc_g = -Rm[..., 2, :] * GRAVITY  # body-frame gravity
         acc = -torch.cross(pqr, uvw, dim=-1) + acc_g
         pqr_dot = -torch.cross(pqr, I * pqr, dim=-1) / I
         rqp_dot = pqr_dot.flip(-1)
@@ -270,7 +274,7 @@ class CrazyFlie(LinearDrone):
         pqr_dot = -np.cross(pqr, I * pqr) / I
         Mm = self._motor_mat()
         wpqr = Mm @ u
-        acc_W = np.array([0.0, 0.0, -9.81]) + Rm @ np.array([0.0, 0.0, wpqr[0]])
+        acc_W = np.array([0.0, 0.0, -GRAVITY]) + Rm @ np.array([0.0, 0.0, wpqr[0]])
         return np.concatenate([deuler_rpy, pqr_dot + wpqr[1:], acc_W])
 
     @staticmethod
@@ -322,7 +326,7 @@ class CrazyFlie(LinearDrone):
         v_W = Rm @ uvw
         mat = np.array([[0, sph / cth, cph / cth], [0, cph, -sph], [1, sph * tth, cph * tth]])
         deuler = mat @ pqr
-        acc = -np.cross(pqr, uvw) - Rm[2, :] * 9.81
+        acc = -np.cross(pqr, uvw) - Rm[2, :] * GRAVITY
         pqr_dot = -np.cross(pqr, I * pqr) / I
         f = np.concatenate([v_W, deuler, acc, pqr_dot[::-1]])
         # LL controller
@@ -432,7 +436,57 @@ class CrazyFlie(LinearDrone):
         u = -torch.einsum("ij,...j->...i", self._K_nom.to(error.device), error)
         return self.clip_action(u)
 
+    # ---- fused GPU step: part A (crazyflie_step kernel: u_ref/reward/RK4 with
+    # the LL LQR per stage/clip/cost/aa+goal mask) + part B
+    # (raytrace_sphere_topk in graph mode: hit rows + lidar mask; well defined
+    # for zero obstacles, the default), replacing a few hundred eager launches
+    def _fused_consts(self, device) -> Tensor:
+        """Every gain, physical constant and limit the step kernel reads, in
+        the order of ops/hip/crazyflie_consts.h."""
+        def build():
+            p = self._params
+            lo, hi = self.state_lim()
+            alo, ahi = self.action_lim()
+            parts = [
+                torch.from_numpy(self._K_nom_np).float().reshape(-1),
+                self._K_ll.reshape(-1),
+                torch.from_numpy(self._motor_mat()).float().reshape(-1),
+                self.u_eq,
+                self.vel_targets_scale,
+                torch.tensor([p["Ixx"], p["Iyy"], p["Izz"], GRAVITY]),
+                lo, hi, alo, ahi,
+                torch.tensor([p["drone_radius"], p["comm_radius"], self._dt]),
+            ]
+            return torch.cat([t.float().cpu() for t in parts]).contiguous()
+
+        return self._dev_const("fused_step", build, device)
+
+    def _fused_step_ok(self, graph: GraphBatch) -> bool:
+        return (not os.environ.get("GCBF_NO_FUSED_ENV") and graph.states.is_cuda
+                and type(self) is CrazyFlie and ops.hip_available()
+                and ops._require_ext().crazyflie_step_fits(
+                    self.num_agents, graph.env_states.n_obs))
+
+    def _step_fused(self, graph: GraphBatch, action: Tensor) -> StepResult:
+        ext = ops._require_ext()
+        p = self._params
+        obs = graph.env_states
+        center, radius = obs.center.contiguous(), obs.radius.contiguous()
+        nxt, mask, reward, cost = ext.crazyflie_step(
+            graph.states.contiguous(), action.contiguous(), center, radius,
+            self._fused_consts(graph.device), self.num_agents, self.n_rays)
+        # part B: lidar rows + lidar mask from the NEXT agent positions
+        next_pos = nxt[:, : self.num_agents, :3].contiguous()
+        ext.raytrace_sphere_graph(next_pos, center, radius, nxt, mask,
+                                  p["n_rays"], self._n_hit, p["comm_radius"])
+        done = torch.zeros(graph.batch_size, dtype=torch.bool, device=graph.device)
+        g = GraphBatch(states=nxt, mask=mask, n_agents=self.num_agents,
+                       n_rays=self.n_rays, env_states=obs)
+        return StepResult(g, reward, cost, done, {})
+
     def step(self, graph: GraphBatch, action: Tensor) -> StepResult:
+        if self._fused_step_ok(graph):
+            return self._step_fused(graph, action)
         action = self.clip_action(action)
         next_agent = self.agent_step_rk4(graph.agent_states, action)
         reward = -((action - self.u_ref(graph)).square().sum(-1)).mean(-1)

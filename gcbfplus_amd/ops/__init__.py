@@ -19,8 +19,10 @@ Op inventory (kernel numbering follows SURVEY.md §2.7):
   gcbf_plus_loss      K10: all GCBF+ hinge losses + metrics in one kernel pair
   di_loss_prep        K10 prologue: u_ref + action clamp + euler + [cur; next]
   proxqp_solve        K11: batched dense QP (labels; no grad)
-  (env_step.hip K5-K8 is launched via env._step_fused; optimizer.hip K13 via
-  ops.optim.FusedAdamW)
+  (env_step.hip K5-K8 is launched via env._step_fused: di_env_step for
+  DoubleIntegrator/DubinsCar, drone3d_step and crazyflie_step as part A with
+  raytrace_sphere_graph as part B for LinearDrone/CrazyFlie; optimizer.hip
+  K13 via ops.optim.FusedAdamW)
 """
 from __future__ import annotations
 

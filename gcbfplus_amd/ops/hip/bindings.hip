@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <c10/hip/HIPStream.h>
 
+#include "crazyflie_consts.h"
 
 // kernel decls (defined in the .hip TUs)
 typedef __bf16 bf16_t_;
@@ -63,6 +64,9 @@ __global__ void drone3d_step_kernel(const float*, const float*, const float*, co
                                     const float*, const float*, float*, bool*, float*,
                                     float*, int, int, int, float, float, float, float,
                                     float);
+__global__ void crazyflie_step_kernel(const float*, const float*, const float*, const float*,
+                                      const float*, float*, bool*, float*, float*, int,
+                                      int, int);
 __global__ void gcbf_loss_bwd_kernel(const float*, const float*, const float*, const float*, const float*, const bool*, const bool*, const float*, const float*, float*, float*, float*, float*, long, int, float, float, float, float, float, float, float);
 
 #define CHECK_IN(x) TORCH_CHECK(x.is_cuda() && x.is_contiguous(), #x " must be contiguous on GPU")
@@ -666,6 +670,49 @@ std::vector<torch::Tensor> drone3d_step(torch::Tensor states, torch::Tensor acti
   return {nxt, mask, reward, cost};
 }
 
+// LDS request of crazyflie_step for N agents / K spheres fits the default
+// per-workgroup limit (env.step falls back to the eager path otherwise)
+bool crazyflie_step_fits(long N, long K) {
+  return crazyflie_step_lds_bytes(N, K) <= CF_LDS_LIMIT;
+}
+
+std::vector<torch::Tensor> crazyflie_step(torch::Tensor states, torch::Tensor action,
+                                          torch::Tensor centers, torch::Tensor radii,
+                                          torch::Tensor consts, long N, long R) {
+  CHECK_IN(states);
+  CHECK_IN(action);
+  CHECK_IN(centers);
+  CHECK_IN(radii);
+  CHECK_IN(consts);
+  TORCH_CHECK(states.dim() == 3 && N > 0 && R >= 0 && states.size(1) == 2 * N + N * R &&
+                  states.size(2) == 12,
+              "states must be (B, 2N + N*R, 12)");
+  long B = states.size(0), K = centers.size(1);
+  TORCH_CHECK(action.dim() == 3 && action.size(0) == B && action.size(1) == N &&
+                  action.size(2) == 4,
+              "action must be (B, N, 4)");
+  TORCH_CHECK(centers.dim() == 3 && centers.size(0) == B && centers.size(2) == 3 &&
+                  radii.dim() == 2 && radii.size(0) == B && radii.size(1) == K,
+              "centers must be (B, K, 3) and radii (B, K)");
+  TORCH_CHECK(consts.numel() == CF_NCONST, "consts must hold ", (int)CF_NCONST, " floats");
+  TORCH_CHECK(crazyflie_step_fits(N, K), "crazyflie_step: N=", N, " K=", K, " needs ",
+              crazyflie_step_lds_bytes(N, K), " bytes of LDS, limit ", CF_LDS_LIMIT);
+  long D = N + 1 + R;
+  auto nxt = torch::empty_like(states);
+  auto mask = torch::empty({B, N, D}, states.options().dtype(torch::kBool));
+  auto reward = torch::empty({B}, states.options());
+  auto cost = torch::empty({B}, states.options());
+  if (B == 0) return {nxt, mask, reward, cost};
+  hipLaunchKernelGGL(crazyflie_step_kernel, dim3(B), dim3(256),
+                     crazyflie_step_lds_bytes(N, K), cur_stream(),
+                     states.data_ptr<float>(), action.data_ptr<float>(),
+                     centers.data_ptr<float>(), radii.data_ptr<float>(),
+                     consts.data_ptr<float>(), nxt.data_ptr<float>(),
+                     mask.data_ptr<bool>(), reward.data_ptr<float>(),
+                     cost.data_ptr<float>(), (int)N, (int)K, (int)R);
+  return {nxt, mask, reward, cost};
+}
+
 std::vector<torch::Tensor> di_loss_prep_fwd(torch::Tensor states, torch::Tensor raw,
                                             torch::Tensor Kmat, long N, double dt,
                                             double inv_m, double comm, double vmax) {
@@ -709,6 +756,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("inv_m"), py::arg("comm"), py::arg("car_r"),
         py::arg("vmax"), py::arg("dyn") = 0);
   m.def("drone3d_step", &drone3d_step, "fused LinearDrone step part A");
+  m.def("crazyflie_step", &crazyflie_step, "fused CrazyFlie step part A (RK4 + LL LQR)",
+        py::arg("states"), py::arg("action"), py::arg("centers"), py::arg("radii"),
+        py::arg("consts"), py::arg("N"), py::arg("R"));
+  m.def("crazyflie_step_fits", &crazyflie_step_fits, py::arg("N"), py::arg("K"));
   m.def("gemm_tn_acc2", &gemm_tn_acc2, py::arg("x"), py::arg("dz"), py::arg("yact"),
         py::arg("actin"), py::arg("dw"), py::arg("db"), py::arg("db2"),
         py::arg("rowgate") = py::none());

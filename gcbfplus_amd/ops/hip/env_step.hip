@@ -366,3 +366,244 @@ void drone3d_step_kernel(const float* __restrict__ states,   // (B, V, 6)
     cost[b] = (red[0][1] + red[1][1] + red[2][1] + red[3][1]) / N;
   }
 }
+
+// ---------------------------------------------------------------------------
+// CrazyFlie (12-state quadrotor, spheres) fused step part A (env/crazyflie.py):
+//   u_ref = clip(-K_nom . err), err = agent - goal with the position part
+//           rescaled to comm when farther than comm
+//   a = clip_action(action); reward = -mean|a - u_ref|^2
+//   RK4 of xdot = f(x) + g u(x) with the low-level LQR (motor thrusts from
+//   the 9-dim world-frame LL state) re-evaluated at every stage, clip_state
+//   cost on the CURRENT state; agent-agent + goal mask on NEXT positions
+// Part B (lidar rows + lidar mask) is raytrace_sphere_topk with graph output.
+// State order (x,y,z, psi,theta,phi, u,v,w, r,q,p). All gains, physical
+// constants and limits come from the `cst` block (crazyflie_consts.h).
+// The 12-float state/stage vectors are only ever indexed by unrolled
+// compile-time constants so they stay in registers.
+// ---------------------------------------------------------------------------
+#include "crazyflie_consts.h"
+
+struct CfState {
+  float v[12];
+};
+
+__device__ __forceinline__ CfState crazyflie_xdot(const CfState& x, const float (&vt)[4],
+                                                  const float* __restrict__ cst) {
+  float sph, cph, sth, cth, sps, cps;
+  sincosf(x.v[5], &sph, &cph);
+  sincosf(x.v[4], &sth, &cth);
+  sincosf(x.v[3], &sps, &cps);
+  const float tth = tanf(x.v[4]);
+  // body -> world rotation (rotmat)
+  const float R00 = cps * cth, R01 = cps * sth * sph - sps * cph,
+              R02 = cps * sth * cph + sps * sph;
+  const float R10 = sps * cth, R11 = sps * sth * sph + cps * cph,
+              R12 = sps * sth * cph - cps * sph;
+  const float R20 = -sth, R21 = cth * sph, R22 = cth * cph;
+  const float u = x.v[6], v = x.v[7], w = x.v[8];
+  const float p = x.v[11], q = x.v[10], r = x.v[9];
+  const float grav = cst[CF_GRAV];
+  const float Ix = cst[CF_INERTIA], Iy = cst[CF_INERTIA + 1], Iz = cst[CF_INERTIA + 2];
+
+  CfState k;
+  // world-frame velocity
+  k.v[0] = R00 * u + R01 * v + R02 * w;
+  k.v[1] = R10 * u + R11 * v + R12 * w;
+  k.v[2] = R20 * u + R21 * v + R22 * w;
+  // euler rates (psi., theta., phi.) = mat . pqr
+  k.v[3] = (sph / cth) * q + (cph / cth) * r;
+  k.v[4] = cph * q - sph * r;
+  k.v[5] = p + (sph * tth) * q + (cph * tth) * r;
+  // body accel: -pqr x uvw + body-frame gravity
+  k.v[6] = -(q * w - r * v) - R20 * grav;
+  k.v[7] = -(r * u - p * w) - R21 * grav;
+  k.v[8] = -(p * v - q * u) - R22 * grav;
+  // pqr. = -pqr x (I pqr) / I, stored flipped (r, q, p)
+  const float Ip = Ix * p, Iq = Iy * q, Ir = Iz * r;
+  k.v[11] = -(q * Ir - r * Iq) / Ix;
+  k.v[10] = -(r * Ip - p * Ir) / Iy;
+  k.v[9] = -(p * Iq - q * Ip) / Iz;
+
+  // low-level LQR on (phi, theta, psi, p, q, r, v_W) - des
+  float d[9];
+  d[0] = x.v[5];
+  d[1] = x.v[4];
+  d[2] = x.v[3];
+  d[3] = p;
+  d[4] = q;
+  d[5] = r - vt[3];
+  d[6] = k.v[0] - vt[0];
+  d[7] = k.v[1] - vt[1];
+  d[8] = k.v[2] - vt[2];
+  float motor[4];
+#pragma unroll
+  for (int m = 0; m < 4; ++m) {
+    float acc = 0.f;
+#pragma unroll
+    for (int j = 0; j < 9; ++j) acc += cst[CF_KLL + m * 9 + j] * d[j];
+    motor[m] = cst[CF_UEQ + m] - acc;
+  }
+  float wpqr[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    float acc = 0.f;
+#pragma unroll
+    for (int m = 0; m < 4; ++m) acc += cst[CF_MM + i * 4 + m] * motor[m];
+    wpqr[i] = acc;
+  }
+  k.v[8] += wpqr[0];
+  k.v[11] += wpqr[1];
+  k.v[10] += wpqr[2];
+  k.v[9] += wpqr[3];
+  return k;
+}
+
+__launch_bounds__(256) __global__
+void crazyflie_step_kernel(const float* __restrict__ states,   // (B, V, 12)
+                           const float* __restrict__ action,   // (B, N, 4)
+                           const float* __restrict__ centers,  // (B, K, 3)
+                           const float* __restrict__ radii,    // (B, K)
+                           const float* __restrict__ cst,      // (CF_NCONST,)
+                           float* __restrict__ next_states,    // (B, V, 12)
+                           bool* __restrict__ mask,            // (B, N, D)
+                           float* __restrict__ reward,         // (B,)
+                           float* __restrict__ cost,           // (B,)
+                           int N, int K, int R) {
+  extern __shared__ float smem[];
+  float* sNext = smem;              // [N][12]
+  float* sCur = sNext + N * 12;     // [N][3] current pos
+  float* sSph = sCur + N * 3;       // [K][4]
+  float* red = sSph + K * 4;        // [4][3] reward / collision / inside partials
+  const int b = blockIdx.x;
+  const int tid = threadIdx.x;
+  const int V = 2 * N + N * R;
+  const int D = N + 1 + R;
+  const float* st = states + (long)b * V * 12;
+  float* nx = next_states + (long)b * V * 12;
+  const float comm = cst[CF_COMM];
+  const float drone_r = cst[CF_DRONE_R];
+  const float dt = cst[CF_DT];
+
+  for (int i = tid; i < K; i += 256) {
+    sSph[i * 4 + 0] = centers[((long)b * K + i) * 3 + 0];
+    sSph[i * 4 + 1] = centers[((long)b * K + i) * 3 + 1];
+    sSph[i * 4 + 2] = centers[((long)b * K + i) * 3 + 2];
+    sSph[i * 4 + 3] = radii[(long)b * K + i];
+  }
+
+  float r_part = 0.f, c_part = 0.f, in_part = 0.f;
+  for (int i = tid; i < N; i += 256) {
+    const float* ap = st + (long)i * 12;
+    const float* gl = st + (long)(N + i) * 12;
+    CfState x;
+    float err[12];
+#pragma unroll
+    for (int s = 0; s < 12; ++s) {
+      x.v[s] = ap[s];
+      err[s] = x.v[s] - gl[s];
+    }
+    sCur[i * 3 + 0] = x.v[0];
+    sCur[i * 3 + 1] = x.v[1];
+    sCur[i * 3 + 2] = x.v[2];
+    // u_ref: position error rescaled to comm when farther than comm
+    const float dist = sqrtf(err[0] * err[0] + err[1] * err[1] + err[2] * err[2]);
+    const float coef = dist > comm ? comm / fmaxf(dist, 1e-4f) : 1.f;
+    err[0] *= coef;
+    err[1] *= coef;
+    err[2] *= coef;
+    float vt[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      float acc = 0.f;
+#pragma unroll
+      for (int s = 0; s < 12; ++s) acc += cst[CF_KNOM + u * 12 + s] * err[s];
+      const float lo = cst[CF_ALO + u], hi = cst[CF_AHI + u];
+      const float uref = fminf(fmaxf(-acc, lo), hi);
+      const float av = fminf(fmaxf(action[((long)b * N + i) * 4 + u], lo), hi);
+      r_part += (av - uref) * (av - uref);
+      vt[u] = av * cst[CF_VTS + u];
+    }
+    // classic RK4, LL controller re-evaluated per stage
+    const float hdt = 0.5f * dt;
+    CfState k = crazyflie_xdot(x, vt, cst);
+    CfState sum = k, xs;
+#pragma unroll
+    for (int s = 0; s < 12; ++s) xs.v[s] = x.v[s] + hdt * k.v[s];
+    k = crazyflie_xdot(xs, vt, cst);
+#pragma unroll
+    for (int s = 0; s < 12; ++s) {
+      sum.v[s] += 2.f * k.v[s];
+      xs.v[s] = x.v[s] + hdt * k.v[s];
+    }
+    k = crazyflie_xdot(xs, vt, cst);
+#pragma unroll
+    for (int s = 0; s < 12; ++s) {
+      sum.v[s] += 2.f * k.v[s];
+      xs.v[s] = x.v[s] + dt * k.v[s];
+    }
+    k = crazyflie_xdot(xs, vt, cst);
+    const float dt6 = dt / 6.f;
+#pragma unroll
+    for (int s = 0; s < 12; ++s) {
+      const float xn = x.v[s] + dt6 * (sum.v[s] + k.v[s]);
+      sNext[i * 12 + s] = fminf(fmaxf(xn, cst[CF_SLO + s]), cst[CF_SHI + s]);
+    }
+  }
+  __syncthreads();
+
+  // cost on CURRENT state
+  for (int i = tid; i < N; i += 256) {
+    const float xi = sCur[i * 3], yi = sCur[i * 3 + 1], zi = sCur[i * 3 + 2];
+    bool coll = false;
+    for (int j = 0; j < N; ++j) {
+      if (j == i) continue;
+      const float dx = xi - sCur[j * 3], dy = yi - sCur[j * 3 + 1],
+                  dz = zi - sCur[j * 3 + 2];
+      coll = coll || (dx * dx + dy * dy + dz * dz < 4.f * drone_r * drone_r);
+    }
+    bool inside = false;
+    for (int k = 0; k < K; ++k) {
+      const float dx = xi - sSph[k * 4], dy = yi - sSph[k * 4 + 1],
+                  dz = zi - sSph[k * 4 + 2];
+      const float rr = sSph[k * 4 + 3] + drone_r;
+      inside = inside || (dx * dx + dy * dy + dz * dz < rr * rr);
+    }
+    c_part += coll ? 1.f : 0.f;
+    in_part += inside ? 1.f : 0.f;
+  }
+
+  // next agent rows + goal rows copied through
+  for (int i = tid; i < N * 12; i += 256) nx[i] = sNext[i];
+  for (int i = tid; i < N * 12; i += 256) nx[N * 12 + i] = st[N * 12 + i];
+
+  // aa + goal mask on NEXT positions (lidar mask written by part B)
+  for (int item = tid; item < N * N; item += 256) {
+    const int i = item / N, j = item % N;
+    const float dx = sNext[i * 12] - sNext[j * 12];
+    const float dy = sNext[i * 12 + 1] - sNext[j * 12 + 1];
+    const float dz = sNext[i * 12 + 2] - sNext[j * 12 + 2];
+    mask[((long)b * N + i) * D + j] =
+        (i != j) && (dx * dx + dy * dy + dz * dz < comm * comm);
+  }
+  for (int i = tid; i < N; i += 256) mask[((long)b * N + i) * D + N] = true;
+
+  r_part = wave_reduce_sum(r_part);
+  c_part = wave_reduce_sum(c_part);
+  in_part = wave_reduce_sum(in_part);
+  const int w = tid >> 6;
+  if ((tid & 63) == 0) {
+    red[w * 3] = r_part;
+    red[w * 3 + 1] = c_part;
+    red[w * 3 + 2] = in_part;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    reward[b] = -(red[0] + red[3] + red[6] + red[9]) / N;
+    // collision.mean() + inside.mean() as torch reduces them on the GPU:
+    // each count times the rounded 1/N, then one add (no fma contraction),
+    // so the cost is bit-equal to the composed path
+    const float inv_n = 1.f / N;
+    cost[b] = __fadd_rn(__fmul_rn(red[1] + red[4] + red[7] + red[10], inv_n),
+                        __fmul_rn(red[2] + red[5] + red[8] + red[11], inv_n));
+  }
+}
