@@ -1,6 +1,7 @@
 // Host-side launchers + pybind for the gcbfplus_amd._C extension (gfx950).
 #include <torch/extension.h>
 #include <hip/hip_runtime.h>
+#include <c10/hip/HIPException.h>
 #include <c10/hip/HIPStream.h>
 
 #include "crazyflie_consts.h"
@@ -83,6 +84,183 @@ static inline bf16_t_* bfp_mut(torch::Tensor& t) {
 }
 
 // ---------------------------------------------------------------------------
+// GEMM-family kernel selection. ONE host function decides, from shapes and
+// the per-call env toggles, which kernel a launcher runs, its dynamic LDS
+// request and (dW) the split-M geometry; the launchers below and the
+// launch-free `gemm_path` query both go through it, so a test can assert
+// the path a shape takes and a threshold change cannot silently leave a
+// kernel uncovered.
+// ---------------------------------------------------------------------------
+enum GemmOp { GEMM_FWD = 0, GEMM_BT = 1, GEMM_TN = 2 };
+enum GemmKernel {
+  GK_DOT, GK_GEMV, GK_SM, GK_BN128, GK_GLDS, GK_BASE,  // Y = act(X W + b) / dX = dZ W^T
+  GK_TN1, GK_TN2, GK_TN3, GK_TN4                       // dW = X^T dZ partial variants
+};
+
+struct GemmPlan {
+  GemmKernel kernel;
+  long Kp;     // fwd: reduction length after the %32 pad (== K when unpadded)
+  size_t lds;  // dynamic LDS request in bytes (0: static only)
+  long gk, gn, S;  // dW: output tile grid and split-M slab count
+  bool remap;      // dW: XCD-aware 1-D launch decode
+};
+
+// Dynamic LDS a workgroup may request on the current device, as the runtime
+// reports it (64 KiB, the project's stated assumption, when there is no
+// device to ask).
+static size_t gemm_lds_limit() {
+  static size_t cached[64] = {0};  // per device ordinal; 0 = not asked yet
+  int dev = 0, v = 0;
+  if (hipGetDevice(&dev) != hipSuccess) {
+    (void)hipGetLastError();
+    return 64 * 1024;
+  }
+  const bool slot = dev >= 0 && dev < 64;
+  if (slot && cached[dev] != 0) return cached[dev];
+  if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess ||
+      v <= 0) {
+    (void)hipGetLastError();
+    return 64 * 1024;
+  }
+  if (slot) cached[dev] = (size_t)v;
+  return (size_t)v;
+}
+
+static GemmPlan gemm_plan(GemmOp op, long M, long K, long N, long actin, bool gated) {
+  GemmPlan p{GK_BASE, K, 0, 0, 0, 0, false};
+  if (op == GEMM_TN) {
+    // kernel variants: 1 = 64x64 transposed-X stage (scalar LDS writes),
+    // 2 = 128x128 tile (slower: same scalar staging), 3 = dW^T orientation
+    // (vector-only LDS staging; measured 154 vs 121 TF on the big training
+    // shape). Shape-deterministic: 3 for large M, 1 for small/launch-bound M.
+    // GCBF_TN_KERNEL overrides for experiments.
+    static int forced = [] {
+      const char* e = getenv("GCBF_TN_KERNEL");
+      return e ? atoi(e) : 0;
+    }();
+    int variant = forced ? forced : (M >= 16384 ? 3 : 1);
+    if (gated && (variant == 2 || variant == 4)) variant = 3;  // gate: 1/3 only
+    bool big = (variant == 2 || variant == 4) && (K >= 128) && (N >= 128);
+    long tk = big ? 128 : 64, tn = big ? 128 : 64;
+    p.gk = (K + tk - 1) / tk;
+    p.gn = (N + tn - 1) / tn;
+    // deterministic split count: aim for ~1024 blocks, depends on shapes only
+    long S = std::min<long>(128, std::max<long>(1, 1024 / std::max<long>(1, p.gk * p.gn)));
+    // keep >= 128 rows per split so small-M dW calls don't pay 64x partial
+    // traffic (S still a pure function of shapes: deterministic)
+    S = std::min<long>(S, std::max<long>(1, (M + 127) / 128));
+    // XCD-aware 1-D launch requires S % 8 == 0 (extra slabs see empty row
+    // ranges and write zero partials — harmless, still deterministic)
+    p.remap = S >= 8;
+    if (p.remap) S = (S + 7) / 8 * 8;
+    p.S = S;
+    p.kernel = big ? (variant == 4 ? GK_TN4 : GK_TN2) : (variant == 3 ? GK_TN3 : GK_TN1);
+    return p;
+  }
+  const size_t b_image = (size_t)(K / 8) * 64 * 8 * sizeof(uint16_t);  // [K/8][64][8]
+  const bool glds_ok = M % 128 == 0 && K % 64 == 0 && getenv("GCBF_GEMM_NOGLDS") == nullptr;
+  if (op == GEMM_FWD) {
+    if (N == 1) {  // thread-per-row dot: gate / CBF head
+      p.kernel = GK_DOT;
+      return p;
+    }
+    if (N <= 16) {
+      p.kernel = GK_GEMV;
+      p.lds = (size_t)K * N * sizeof(uint16_t);
+      return p;
+    }
+    if ((K % 32) != 0) {  // zero-pad K for the MFMA path, then select again
+      GemmPlan q = gemm_plan(op, M, (K + 31) / 32 * 32, N, actin, gated);
+      q.Kp = (K + 31) / 32 * 32;
+      return q;
+    }
+    if (M <= 16384) {
+      // small-M tile: 32x64 so mid-size layers still fill 256 CUs
+      p.kernel = GK_SM;
+      p.lds = b_image + 32 * 40 * sizeof(uint16_t);
+    } else if (N >= 128 && (N % 128) == 0 && getenv("GCBF_GEMM_BN128") != nullptr) {
+      // BN=128: halves A re-reads for the 256-wide layers
+      p.kernel = GK_BN128;
+      p.lds = 2 * b_image + 128 * 40 * sizeof(uint16_t);
+    } else if (glds_ok) {
+      // glds-pipelined path (double-buffered direct-to-LDS A staging)
+      p.kernel = GK_GLDS;
+      p.lds = b_image + 2 * 128 * 64 * sizeof(uint16_t);
+    } else {
+      p.kernel = GK_BASE;
+      p.lds = b_image + 128 * 40 * sizeof(uint16_t);
+    }
+    return p;
+  }
+  // GEMM_BT: K is the reduction dim (dZ cols), N the output width (W rows)
+  if (M <= 16384) {
+    p.kernel = GK_SM;
+    p.lds = b_image + 32 * 40 * sizeof(uint16_t);
+  } else if (actin == 0 && glds_ok) {
+    p.kernel = GK_GLDS;
+    p.lds = b_image + 2 * 128 * 64 * sizeof(uint16_t);
+  } else {
+    p.kernel = GK_BASE;
+    p.lds = b_image + 128 * 40 * sizeof(uint16_t);
+  }
+  return p;
+}
+
+static const char* gemm_kernel_name(GemmKernel k) {
+  switch (k) {
+    case GK_DOT: return "dot";
+    case GK_GEMV: return "gemv";
+    case GK_SM: return "sm";
+    case GK_BN128: return "bn128";
+    case GK_GLDS: return "glds";
+    case GK_BASE: return "base";
+    case GK_TN1: return "tn1";
+    case GK_TN2: return "tn2";
+    case GK_TN3: return "tn3";
+    case GK_TN4: return "tn4";
+  }
+  return "?";
+}
+
+// Refuse a launch whose dynamic LDS request the device cannot serve: the
+// runtime would reject it and the output would be uninitialised memory.
+static void check_lds(const char* what, const GemmPlan& p, long M, long K, long N) {
+  const size_t limit = gemm_lds_limit();
+  TORCH_CHECK(p.lds <= limit, what, ": M=", M, " K=", K, " N=", N, " (", gemm_kernel_name(p.kernel),
+              " kernel) needs ", p.lds, " bytes of LDS, device limit ", limit);
+}
+
+// Launch-free dispatch query: which kernel `op` ("fwd" gemm_bias_act, "bt"
+// gemm_bt, "tn" gemm_tn/_acc/_acc2) runs for this shape under the current
+// env toggles. fwd: "dot" | "gemv" | "sm" | "glds" | "base" | "bn128",
+// prefixed "pad->" when K is zero-padded to %32 first; bt: the same names
+// with a "_bt" suffix; tn: "tn<variant> S=<slabs> remap=<0|1>".
+std::string gemm_path(const std::string& op, long M, long K, long N, long actin, bool gated) {
+  TORCH_CHECK(M > 0 && K > 0 && N > 0, "gemm_path: M, K, N must be positive");
+  if (op == "fwd") {
+    GemmPlan p = gemm_plan(GEMM_FWD, M, K, N, 0, false);
+    return std::string(p.Kp != K ? "pad->" : "") + gemm_kernel_name(p.kernel);
+  }
+  if (op == "bt") {
+    TORCH_CHECK(K % 32 == 0, "BT path needs reduction dim % 32 == 0");
+    return std::string(gemm_kernel_name(gemm_plan(GEMM_BT, M, K, N, actin, false).kernel)) + "_bt";
+  }
+  TORCH_CHECK(op == "tn", "gemm_path: op must be \"fwd\", \"bt\" or \"tn\"");
+  GemmPlan p = gemm_plan(GEMM_TN, M, K, N, actin, gated);
+  return std::string(gemm_kernel_name(p.kernel)) + " S=" + std::to_string(p.S) +
+         " remap=" + (p.remap ? "1" : "0");
+}
+
+// Every path a default environment (no GCBF_* toggle set) can select, in
+// `gemm_path` spelling with the dW slab count left out.
+std::vector<std::string> gemm_default_paths() {
+  return {"dot",   "gemv",    "sm",      "glds",         "base",         "pad->sm",
+          "pad->glds", "pad->base", "sm_bt", "glds_bt", "base_bt",
+          "tn1 remap=0", "tn1 remap=1", "tn3 remap=1"};
+}
+
+long gemm_lds_limit_bytes() { return (long)gemm_lds_limit(); }
+
 torch::Tensor gemm_bias_act(torch::Tensor x, torch::Tensor w, torch::Tensor bias, long act) {
   CHECK_IN(x);
   CHECK_IN(w);
@@ -92,28 +270,33 @@ torch::Tensor gemm_bias_act(torch::Tensor x, torch::Tensor w, torch::Tensor bias
   long M = x.size(0), K = x.size(1), N = w.size(1);
   TORCH_CHECK(w.size(0) == K, "K mismatch");
 
+  const GemmPlan plan = gemm_plan(GEMM_FWD, M, K, N, 0, false);
   // pad K to a multiple of 32 for the MFMA path (the gather op emits padded
   // inputs on the hot path; this is the generic fallback)
-  if (N > 16 && (K % 32) != 0) {
-    long Kp = (K + 31) / 32 * 32;
+  if (plan.Kp != K) {
+    long Kp = plan.Kp;
     auto xp = torch::zeros({M, Kp}, x.options());
     xp.narrow(1, 0, K).copy_(x);
     auto wp = torch::zeros({Kp, N}, w.options());
     wp.narrow(0, 0, K).copy_(w);
     return gemm_bias_act(xp, wp, bias, act);
   }
+  check_lds("gemm_bias_act", plan, M, K, N);
 
   auto stream = cur_stream();
-  if (N <= 16) {
+  const size_t smem = plan.lds;
+  if (plan.kernel == GK_DOT || plan.kernel == GK_GEMV) {
     // small-N head/gate outputs come out in f32: the CBF h enters the
     // h_dot = (h_next - h)/dt finite difference where bf16 storage would
     // cancel catastrophically (bf16 ulp at |h|~1 is 0.008, signal ~0.03h)
     auto y = torch::empty({M, N}, x.options().dtype(torch::kFloat32));
-    if (N == 1) {  // thread-per-row dot: gate / CBF head
+    if (M == 0) return y;
+    if (plan.kernel == GK_DOT) {  // thread-per-row dot: gate / CBF head
       dim3 grid((M + 255) / 256);
       auto launch = [&](auto kernel) {
         hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, bfp(x), bfp(w),
                            bias.data_ptr<float>(), y.data_ptr<float>(), M, (int)K);
+        C10_HIP_KERNEL_LAUNCH_CHECK();
       };
       if (act == 0) launch(dot_bias_act_kernel<0>);
       else if (act == 1) launch(dot_bias_act_kernel<1>);
@@ -121,10 +304,10 @@ torch::Tensor gemm_bias_act(torch::Tensor x, torch::Tensor w, torch::Tensor bias
       return y;
     }
     dim3 grid((M + 3) / 4);
-    size_t smem = (size_t)K * N * sizeof(uint16_t);
     auto launch = [&](auto kernel) {
       hipLaunchKernelGGL(kernel, grid, dim3(256), smem, stream, bfp(x), bfp(w),
                          bias.data_ptr<float>(), y.data_ptr<float>(), (int)M, (int)N, (int)K);
+      C10_HIP_KERNEL_LAUNCH_CHECK();
     };
     if (act == 0) launch(gemv_bias_act_kernel<0, float>);
     else if (act == 1) launch(gemv_bias_act_kernel<1, float>);
@@ -132,47 +315,45 @@ torch::Tensor gemm_bias_act(torch::Tensor x, torch::Tensor w, torch::Tensor bias
     return y;
   }
   auto y = torch::empty({M, N}, x.options());
-  if (M <= 16384) {
-    // small-M tile: 32x64 so mid-size layers still fill 256 CUs
+  if (M == 0) return y;
+  if (plan.kernel == GK_SM) {
     dim3 grid((M + 31) / 32, (N + 63) / 64);
-    size_t smem = (size_t)(K / 8) * 64 * 8 * sizeof(uint16_t) + 32 * 40 * sizeof(uint16_t);
     auto launch = [&](auto kernel) {
       hipLaunchKernelGGL(kernel, grid, dim3(256), smem, stream, bfp(x), bfp(w),
                          bias.data_ptr<float>(), bfp_mut(y), (const bf16_t_*)nullptr,
                          (int)M, (int)N, (int)K);
+      C10_HIP_KERNEL_LAUNCH_CHECK();
     };
     if (act == 0) launch(gemm_bias_act_sm_kernel<0, false, 0>);
     else if (act == 1) launch(gemm_bias_act_sm_kernel<1, false, 0>);
     else launch(gemm_bias_act_sm_kernel<2, false, 0>);
-  } else if (N >= 128 && (N % 128) == 0 && getenv("GCBF_GEMM_BN128") != nullptr) {
-    // BN=128: halves A re-reads for the 256-wide layers
+  } else if (plan.kernel == GK_BN128) {
     dim3 grid((M + 127) / 128, N / 128);
-    size_t smem = (size_t)(K / 8) * 128 * 8 * sizeof(uint16_t) + 128 * 40 * sizeof(uint16_t);
     auto launch = [&](auto kernel) {
       hipLaunchKernelGGL(kernel, grid, dim3(256), smem, stream, bfp(x), bfp(w),
                          bias.data_ptr<float>(), bfp_mut(y), (int)M, (int)N, (int)K);
+      C10_HIP_KERNEL_LAUNCH_CHECK();
     };
     if (act == 0) launch(gemm_bias_act_bn128_kernel<0>);
     else if (act == 1) launch(gemm_bias_act_bn128_kernel<1>);
     else launch(gemm_bias_act_bn128_kernel<2>);
-  } else if (M % 128 == 0 && K % 64 == 0 && getenv("GCBF_GEMM_NOGLDS") == nullptr) {
-    // glds-pipelined path (double-buffered direct-to-LDS A staging)
+  } else if (plan.kernel == GK_GLDS) {
     dim3 grid(M / 128, (N + 63) / 64);
-    size_t smem = (size_t)(K / 8) * 64 * 8 * sizeof(uint16_t) + 2 * 128 * 64 * sizeof(uint16_t);
     auto launch = [&](auto kernel) {
       hipLaunchKernelGGL(kernel, grid, dim3(256), smem, stream, bfp(x), bfp(w),
                          bias.data_ptr<float>(), bfp_mut(y), (int)M, (int)N, (int)K);
+      C10_HIP_KERNEL_LAUNCH_CHECK();
     };
     if (act == 0) launch(gemm_bias_act_glds_kernel<0, false>);
     else if (act == 1) launch(gemm_bias_act_glds_kernel<1, false>);
     else launch(gemm_bias_act_glds_kernel<2, false>);
   } else {
     dim3 grid((M + 127) / 128, (N + 63) / 64);
-    size_t smem = (size_t)(K / 8) * 64 * 8 * sizeof(uint16_t) + 128 * 40 * sizeof(uint16_t);
     auto launch = [&](auto kernel) {
       hipLaunchKernelGGL(kernel, grid, dim3(256), smem, stream, bfp(x), bfp(w),
                          bias.data_ptr<float>(), bfp_mut(y), (const bf16_t_*)nullptr,
                          (int)M, (int)N, (int)K);
+      C10_HIP_KERNEL_LAUNCH_CHECK();
     };
     if (act == 0) launch(gemm_bias_act_kernel<0, false, 0>);
     else if (act == 1) launch(gemm_bias_act_kernel<1, false, 0>);
@@ -187,8 +368,10 @@ torch::Tensor act_bwd(torch::Tensor dy, torch::Tensor y, long act) {
   if (act == 0) return dy;
   auto dz = torch::empty_like(dy);
   long n = dy.numel();
+  if (n == 0) return dz;
   hipLaunchKernelGGL(act_bwd_kernel, dim3((n + 255) / 256), dim3(256), 0, cur_stream(),
                      bfp(dy), bfp(y), bfp_mut(dz), n, (int)act);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return dz;
 }
 
@@ -201,29 +384,9 @@ std::vector<torch::Tensor> gemm_tn_impl(torch::Tensor x, torch::Tensor dz,
   CHECK_IN(dz);
   long M = x.size(0), K = x.size(1), N = dz.size(1);
   TORCH_CHECK(dz.size(0) == M);
-  // kernel variants: 1 = 64x64 transposed-X stage (scalar LDS writes),
-  // 2 = 128x128 tile (slower: same scalar staging), 3 = dW^T orientation
-  // (vector-only LDS staging; measured 154 vs 121 TF on the big training
-  // shape). Shape-deterministic: 3 for large M, 1 for small/launch-bound M.
-  // GCBF_TN_KERNEL overrides for experiments.
-  static int forced = [] {
-    const char* e = getenv("GCBF_TN_KERNEL");
-    return e ? atoi(e) : 0;
-  }();
-  int variant = forced ? forced : (M >= 16384 ? 3 : 1);
-  if (rowgate && (variant == 2 || variant == 4)) variant = 3;  // gate: 1/3 only
-  bool big = (variant == 2 || variant == 4) && (K >= 128) && (N >= 128);
-  long tk = big ? 128 : 64, tn = big ? 128 : 64;
-  long gk = (K + tk - 1) / tk, gn = (N + tn - 1) / tn;
-  // deterministic split count: aim for ~1024 blocks, depends on shapes only
-  long S = std::min<long>(128, std::max<long>(1, 1024 / std::max<long>(1, gk * gn)));
-  // keep >= 128 rows per split so small-M dW calls don't pay 64x partial
-  // traffic (S still a pure function of shapes: deterministic)
-  S = std::min<long>(S, std::max<long>(1, (M + 127) / 128));
-  // XCD-aware 1-D launch requires S % 8 == 0 (extra slabs see empty row
-  // ranges and write zero partials — harmless, still deterministic)
-  bool remap = S >= 8;
-  if (remap) S = (S + 7) / 8 * 8;
+  const GemmPlan plan = gemm_plan(GEMM_TN, M, K, N, actin, rowgate.has_value());
+  const long gk = plan.gk, gn = plan.gn, S = plan.S;
+  const bool remap = plan.remap;
 
   auto opts = x.options().dtype(torch::kFloat32);
   auto partial = torch::empty({S, K, N}, opts);
@@ -241,22 +404,24 @@ std::vector<torch::Tensor> gemm_tn_impl(torch::Tensor x, torch::Tensor dz,
                        stream, bfp(x), bfp(dz), ya, rg, partial.data_ptr<float>(),
                        db_partial.data_ptr<float>(), (int)M, (int)N, (int)K, (int)S,
                        remap ? 1 : 0);
+    C10_HIP_KERNEL_LAUNCH_CHECK();
   };
   auto launch24 = [&](auto kernel) {  // kernels 2/4: no rowgate param
     hipLaunchKernelGGL(kernel, remap ? dim3(gk * gn * S) : dim3(gk, gn, S), dim3(256), 0,
                        stream, bfp(x), bfp(dz), ya, partial.data_ptr<float>(),
                        db_partial.data_ptr<float>(), (int)M, (int)N, (int)K, (int)S,
                        remap ? 1 : 0);
+    C10_HIP_KERNEL_LAUNCH_CHECK();
   };
-  if (big && variant == 4) {
+  if (plan.kernel == GK_TN4) {
     if (actin == 1) launch24(gemm_tn_partial4_kernel<1>);
     else if (actin == 2) launch24(gemm_tn_partial4_kernel<2>);
     else launch24(gemm_tn_partial4_kernel<0>);
-  } else if (big) {
+  } else if (plan.kernel == GK_TN2) {
     if (actin == 1) launch24(gemm_tn_partial2_kernel<1>);
     else if (actin == 2) launch24(gemm_tn_partial2_kernel<2>);
     else launch24(gemm_tn_partial2_kernel<0>);
-  } else if (variant == 3) {
+  } else if (plan.kernel == GK_TN3) {
     if (actin == 1) launch(gemm_tn_partial3_kernel<1>);
     else if (actin == 2) launch(gemm_tn_partial3_kernel<2>);
     else launch(gemm_tn_partial3_kernel<0>);
@@ -270,6 +435,7 @@ std::vector<torch::Tensor> gemm_tn_impl(torch::Tensor x, torch::Tensor dz,
                      dw.data_ptr<float>(), db.data_ptr<float>(),
                      db2 ? db2->data_ptr<float>() : nullptr, K * N, (int)N, (int)S,
                      acc ? 1 : 0);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return {dw, db};
 }
 
@@ -319,28 +485,31 @@ torch::Tensor gemm_bt(torch::Tensor dz, torch::Tensor w, torch::Tensor yact, lon
     zb = torch::zeros({std::max<long>(N, 512)}, dz.options().dtype(torch::kFloat32));
   const float* bias = zb.data_ptr<float>();
   const bf16_t_* ya = actin ? bfp(yact) : nullptr;
-  if (M <= 16384) {
+  if (M == 0) return y;
+  const GemmPlan plan = gemm_plan(GEMM_BT, M, K, N, actin, false);
+  check_lds("gemm_bt", plan, M, K, N);
+  const size_t smem = plan.lds;
+  if (plan.kernel == GK_SM) {
     dim3 grid((M + 31) / 32, (N + 63) / 64);
-    size_t smem = (size_t)(K / 8) * 64 * 8 * sizeof(uint16_t) + 32 * 40 * sizeof(uint16_t);
     auto launch = [&](auto kernel) {
       hipLaunchKernelGGL(kernel, grid, dim3(256), smem, stream, bfp(dz), bfp(w), bias,
                          bfp_mut(y), ya, (int)M, (int)N, (int)K);
+      C10_HIP_KERNEL_LAUNCH_CHECK();
     };
     if (actin == 1) launch(gemm_bias_act_sm_kernel<0, true, 1>);
     else if (actin == 2) launch(gemm_bias_act_sm_kernel<0, true, 2>);
     else launch(gemm_bias_act_sm_kernel<0, true, 0>);
-  } else if (actin == 0 && M % 128 == 0 && K % 64 == 0 &&
-             getenv("GCBF_GEMM_NOGLDS") == nullptr) {
+  } else if (plan.kernel == GK_GLDS) {
     dim3 grid(M / 128, (N + 63) / 64);
-    size_t smem = (size_t)(K / 8) * 64 * 8 * sizeof(uint16_t) + 2 * 128 * 64 * sizeof(uint16_t);
     hipLaunchKernelGGL((gemm_bias_act_glds_kernel<0, true>), grid, dim3(256), smem, stream,
                        bfp(dz), bfp(w), bias, bfp_mut(y), (int)M, (int)N, (int)K);
+    C10_HIP_KERNEL_LAUNCH_CHECK();
   } else {
     dim3 grid((M + 127) / 128, (N + 63) / 64);
-    size_t smem = (size_t)(K / 8) * 64 * 8 * sizeof(uint16_t) + 128 * 40 * sizeof(uint16_t);
     auto launch = [&](auto kernel) {
       hipLaunchKernelGGL(kernel, grid, dim3(256), smem, stream, bfp(dz), bfp(w), bias,
                          bfp_mut(y), ya, (int)M, (int)N, (int)K);
+      C10_HIP_KERNEL_LAUNCH_CHECK();
     };
     if (actin == 1) launch(gemm_bias_act_kernel<0, true, 1>);
     else if (actin == 2) launch(gemm_bias_act_kernel<0, true, 2>);
@@ -771,6 +940,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "flat-buffer global-norm-clip AdamW with finite guard (K13)");
   m.def("proxqp_solve", &proxqp_solve_hip, "batched dense QP, one wave per problem (K11)");
   m.def("gemm_bias_act", &gemm_bias_act, "Y = act(X@W + b), MFMA bf16");
+  m.def("gemm_path", &gemm_path, "kernel a GEMM-family op selects for a shape (no launch)",
+        py::arg("op"), py::arg("M"), py::arg("K"), py::arg("N"), py::arg("actin") = 0,
+        py::arg("gated") = false);
+  m.def("gemm_default_paths", &gemm_default_paths,
+        "every gemm_path a default environment can select (dW slab count left out)");
+  m.def("gemm_lds_limit", &gemm_lds_limit_bytes,
+        "dynamic LDS bytes a workgroup may request on the current device");
   m.def("act_bwd", &act_bwd, "dZ = dY * act'(Y)");
   m.def("gemm_bt", &gemm_bt, "dX = dZ @ W^T (transposed B-stage, no copy)");
   m.def("gemm_tn", &gemm_tn, "dW = X^T dZ, db = colsum dZ (deterministic)",

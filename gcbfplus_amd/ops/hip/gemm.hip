@@ -38,7 +38,9 @@ __device__ __forceinline__ void stage_B_image(const bf16_t* __restrict__ W, bf16
       const int k = c >> 3;
       const int co = (c & 7) * 8;
       bf16_t v[8];
-      if (n0 + co + 7 < N) {
+      // b128 loads need 16-B alignment: row base k*N is aligned only when
+      // N % 8 == 0 (N = 20, 70, ... take the scalar path for every chunk)
+      if (n0 + co + 7 < N && (N & 7) == 0) {
         *(bf16x8*)v = *(const bf16x8*)(W + (long)k * N + n0 + co);
       } else {
 #pragma unroll

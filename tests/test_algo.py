@@ -222,7 +222,8 @@ def test_trainer_parity_helpers():
     nrm = centered_norm([-1.0, -3.0], [2.0])
     assert nrm.halfrange == 3.0 and nrm.vcenter == 0
 
-    env = make_env("DoubleIntegrator", num_agents=4, area_size=2.0, max_step=4)
+    # the net below lives on the CPU: keep the env there on a GPU machine too
+    env = make_env("DoubleIntegrator", num_agents=4, area_size=2.0, max_step=4, device="cpu")
     g = env.reset(1, np.random.default_rng(0))
     net = CBFNet(env.node_dim, env.edge_dim, 1)
     cbf = lambda gr: net(gr, env.edge_feats(gr))

@@ -681,7 +681,11 @@ def test_gemm_tn_rowgate_matches_masked():
         dz = (torch.randn(M, 128, device="cuda") * 0.5).to(torch.bfloat16)
         gate = torch.rand(M, device="cuda") < 0.5
         dw, db = _C.gemm_tn(x, dz, dz, 0, gate)
-        dzm = dz * gate[:, None]
-        dw_ref, db_ref = _C.gemm_tn(x, dzm.to(torch.bfloat16), dzm, 0)
+        # float64 reference on the host (not the same kernel on pre-masked
+        # input, which would share a dropped row with the kernel under test)
+        dzm = dz.double().cpu() * gate.cpu()[:, None]
+        dw_ref = (x.double().cpu().t() @ dzm).float()
+        db_ref = dzm.sum(0).float()
+        dw, db = dw.cpu(), db.cpu()
         assert torch.allclose(dw, dw_ref, atol=1e-3), (M, (dw - dw_ref).abs().max())
         assert torch.allclose(db, db_ref, atol=1e-3), (M, (db - db_ref).abs().max())
