@@ -499,6 +499,20 @@ class CrazyFlie(LinearDrone):
         action = self.clip_action(action)
         return graph.with_agent_states(self.agent_step_rk4(graph.agent_states, action))
 
+    def loss_prep(self, graph: GraphBatch, raw: Tensor):
+        """Fused GCBF+ loss prologue: u_ref -> action = 2*raw + u_ref
+        (unclamped, as the eager branch of ``_loss`` takes the action loss)
+        -> RK4 next state of the clamped action -> [states; next_states],
+        differentiable w.r.t. ``raw``. Only for the exact class on the GPU
+        with the extension (subclasses override dynamics/u_ref); ``None``
+        sends ``_loss`` down its eager branch. GCBF_NO_FUSED_PREP forces
+        that branch."""
+        if (type(self) is not CrazyFlie or not graph.states.is_cuda
+                or os.environ.get("GCBF_NO_FUSED_PREP") or not ops.hip_available()):
+            return None
+        return ops.crazyflie_loss_prep(graph.states, raw,
+                                       self._fused_consts(graph.device), self.num_agents)
+
     # lidar: 3D fan over params['n_rays'] beams, top-n_hit returns
     def get_lidar_hits(self, agent_pos: Tensor, obstacles: Sphere) -> Tensor:
         from .utils import get_lidar

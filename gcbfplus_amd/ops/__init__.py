@@ -18,6 +18,8 @@ Op inventory (kernel numbering follows SURVEY.md §2.7):
   raytrace_rect       K1: 2D LiDAR fan vs rectangle set (no grad)
   gcbf_plus_loss      K10: all GCBF+ hinge losses + metrics in one kernel pair
   di_loss_prep        K10 prologue: u_ref + action clamp + euler + [cur; next]
+  crazyflie_loss_prep K10 prologue (CrazyFlie): u_ref + unclamped action + RK4 with
+                      the low-level LQR + [cur; next]; dual-number backward
   proxqp_solve        K11: batched dense QP (labels; no grad)
   (env_step.hip K5-K8 is launched via env._step_fused: di_env_step for
   DoubleIntegrator/DubinsCar, drone3d_step and crazyflie_step as part A with
@@ -514,3 +516,49 @@ def di_loss_prep(states: Tensor, raw: Tensor, K: Tensor, n_agents: int,
     pos = agent[..., :2] + agent[..., 2:] * dt
     nxt = torch.cat([torch.cat([pos, vel], -1), states[:, N:]], dim=1)
     return action, torch.cat([states, nxt], dim=0)
+
+
+# --------------------------------------------------------------------------
+# fused GCBF+ minibatch prologue for CrazyFlie
+# --------------------------------------------------------------------------
+class _CrazyFlieLossPrepHIP(torch.autograd.Function):
+    """u_ref (env/crazyflie.py) -> action = 2*raw + u_ref (UNCLAMPED, as the
+    action loss takes it) -> next = clip_state(RK4(x, clamp(action) * scale))
+    with the low-level LQR per stage -> big = [states; next_states]: one
+    kernel each way instead of a few hundred eager launches. The backward
+    recomputes the RK4 in dual-number arithmetic, one thread per action
+    component. Gradient flows to ``raw`` only (minibatch states are leaves)."""
+
+    @staticmethod
+    def forward(ctx, states, raw, consts, n_agents):
+        ext = _require_ext()
+        states, raw, consts = states.contiguous(), raw.contiguous(), consts.contiguous()
+        action, big = ext.crazyflie_loss_prep_fwd(states, raw, consts, n_agents)
+        # the unclamped action carries u_ref and both clamp masks: raw is not kept
+        ctx.save_for_backward(states, consts, action)
+        ctx.n_agents = n_agents
+        return action, big
+
+    @staticmethod
+    def backward(ctx, daction, dbig):
+        ext = _require_ext()
+        states, consts, action = ctx.saved_tensors
+        if daction is None:
+            daction = torch.zeros_like(action)
+        if dbig is None:
+            B, V, S = states.shape
+            dbig = states.new_zeros(2 * B, V, S)
+        draw = ext.crazyflie_loss_prep_bwd(
+            states, consts, action, daction.contiguous(), dbig.contiguous(),
+            ctx.n_agents)
+        return None, draw, None, None
+
+
+def crazyflie_loss_prep(states: Tensor, raw: Tensor, consts: Tensor, n_agents: int):
+    """Returns (action (B,N,4) = 2*raw + u_ref unclamped, big_states
+    (2B,V,12) = [states; next_states]). states (B,V,12) with agent rows
+    [:N] and goal rows [N:2N]; consts is CrazyFlie._fused_consts. GPU only
+    (HIP, capture-safe); CPU callers take the composed env path."""
+    if not states.is_cuda:
+        raise NotImplementedError("CPU path goes through env.u_ref / env.forward_graph")
+    return _CrazyFlieLossPrepHIP.apply(states, raw, consts, n_agents)

@@ -4,6 +4,9 @@
 #include <c10/hip/HIPException.h>
 #include <c10/hip/HIPStream.h>
 
+#include <climits>
+#include <cstdint>
+
 #include "crazyflie_consts.h"
 
 // kernel decls (defined in the .hip TUs)
@@ -57,6 +60,11 @@ __global__ void di_loss_prep_fwd_kernel(const float*, const float*, const float*
 __global__ void di_loss_prep_bwd_kernel(const float*, const float*, const float*, const float*,
                                         const float*, const float*, float*, int, int, int,
                                         float, float, float, float);
+__global__ void crazyflie_loss_prep_fwd_kernel(const float*, const float*, const float*, float*,
+                                               float*, int, int, int);
+__global__ void crazyflie_loss_prep_bwd_kernel(const float*, const float*, const float*,
+                                               const float*, const float*, float*, int, int,
+                                               int);
 template <int DYN>
 __global__ void env_step2d_kernel(const float*, const float*, const float*, const float*,
                                   float*, bool*, float*, float*, int, int, int, float,
@@ -915,9 +923,85 @@ torch::Tensor di_loss_prep_bwd(torch::Tensor states, torch::Tensor raw, torch::T
   return draw;
 }
 
+// CrazyFlie loss prologue: contiguous f32 on the GPU, shapes that the kernels
+// index by, the whole constant block
+// (rows are moved as float4: 16-byte aligned base)
+#define CHECK_F32(x) \
+  TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.scalar_type() == torch::kFloat32 && \
+                  reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0, \
+              #x " must be a contiguous, 16-byte aligned float32 GPU tensor")
+
+static void crazyflie_loss_prep_check(const torch::Tensor& states, const torch::Tensor& consts,
+                                      long N) {
+  CHECK_F32(states);
+  CHECK_F32(consts);
+  TORCH_CHECK(states.dim() == 3 && states.size(2) == 12, "states must be (B, V, 12)");
+  TORCH_CHECK(N > 0 && states.size(1) >= 2 * N, "states must hold N agent and N goal rows");
+  TORCH_CHECK(consts.numel() == CF_NCONST, "consts must hold ", (int)CF_NCONST, " floats");
+  TORCH_CHECK(consts.device() == states.device(), "consts must be on the device of states");
+  TORCH_CHECK(states.size(0) <= INT_MAX / 2 && states.size(1) <= INT_MAX,
+              "states batch too large");
+}
+
+static void crazyflie_loss_prep_check_bn4(const torch::Tensor& t, const char* name,
+                                          const torch::Tensor& states, long N) {
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.scalar_type() == torch::kFloat32 &&
+                  reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,
+              name, " must be a contiguous, 16-byte aligned float32 GPU tensor");
+  TORCH_CHECK(t.dim() == 3 && t.size(0) == states.size(0) && t.size(1) == N && t.size(2) == 4,
+              name, " must be (B, N, 4)");
+  TORCH_CHECK(t.device() == states.device(), name, " must be on the device of states");
+}
+
+std::vector<torch::Tensor> crazyflie_loss_prep_fwd(torch::Tensor states, torch::Tensor raw,
+                                                   torch::Tensor consts, long N) {
+  crazyflie_loss_prep_check(states, consts, N);
+  crazyflie_loss_prep_check_bn4(raw, "raw", states, N);
+  long B = states.size(0), V = states.size(1);
+  auto action = torch::empty({B, N, 4}, states.options());
+  auto big = torch::empty({2 * B, V, 12}, states.options());
+  long rows = 2 * B * V;
+  if (rows == 0) return {action, big};
+  hipLaunchKernelGGL(crazyflie_loss_prep_fwd_kernel, dim3((rows + 255) / 256), dim3(256), 0,
+                     cur_stream(), states.data_ptr<float>(), raw.data_ptr<float>(),
+                     consts.data_ptr<float>(), action.data_ptr<float>(),
+                     big.data_ptr<float>(), (int)B, (int)V, (int)N);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return {action, big};
+}
+
+torch::Tensor crazyflie_loss_prep_bwd(torch::Tensor states, torch::Tensor consts,
+                                      torch::Tensor action, torch::Tensor daction,
+                                      torch::Tensor dbig, long N) {
+  crazyflie_loss_prep_check(states, consts, N);
+  crazyflie_loss_prep_check_bn4(action, "action", states, N);
+  crazyflie_loss_prep_check_bn4(daction, "daction", states, N);
+  CHECK_F32(dbig);
+  long B = states.size(0), V = states.size(1);
+  TORCH_CHECK(dbig.dim() == 3 && dbig.size(0) == 2 * B && dbig.size(1) == V &&
+                  dbig.size(2) == 12 && dbig.device() == states.device(),
+              "dbig must be (2B, V, 12) on the device of states");
+  auto draw = torch::empty_like(action);
+  long total = B * N * 4;
+  if (total == 0) return draw;
+  hipLaunchKernelGGL(crazyflie_loss_prep_bwd_kernel, dim3((total + 255) / 256), dim3(256), 0,
+                     cur_stream(), states.data_ptr<float>(), consts.data_ptr<float>(),
+                     action.data_ptr<float>(), daction.data_ptr<float>(),
+                     dbig.data_ptr<float>(), draw.data_ptr<float>(), (int)B, (int)V, (int)N);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return draw;
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("di_loss_prep_fwd", &di_loss_prep_fwd);
   m.def("di_loss_prep_bwd", &di_loss_prep_bwd);
+  m.def("crazyflie_loss_prep_fwd", &crazyflie_loss_prep_fwd,
+        "fused CrazyFlie loss prologue: (action unclamped, [states; next_states])",
+        py::arg("states"), py::arg("raw"), py::arg("consts"), py::arg("N"));
+  m.def("crazyflie_loss_prep_bwd", &crazyflie_loss_prep_bwd,
+        "gradient of the CrazyFlie loss prologue w.r.t. raw (dual-number RK4)",
+        py::arg("states"), py::arg("consts"), py::arg("action"), py::arg("daction"),
+        py::arg("dbig"), py::arg("N"));
   m.def("di_env_step", &di_env_step,
         "fused 2D env step, dyn=0 DI / dyn=1 Dubins (K5-K8)",
         py::arg("states"), py::arg("action"), py::arg("points"),

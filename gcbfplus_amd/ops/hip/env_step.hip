@@ -381,82 +381,10 @@ void drone3d_step_kernel(const float* __restrict__ states,   // (B, V, 6)
 // The 12-float state/stage vectors are only ever indexed by unrolled
 // compile-time constants so they stay in registers.
 // ---------------------------------------------------------------------------
-#include "crazyflie_consts.h"
-
-struct CfState {
-  float v[12];
-};
-
-__device__ __forceinline__ CfState crazyflie_xdot(const CfState& x, const float (&vt)[4],
-                                                  const float* __restrict__ cst) {
-  float sph, cph, sth, cth, sps, cps;
-  sincosf(x.v[5], &sph, &cph);
-  sincosf(x.v[4], &sth, &cth);
-  sincosf(x.v[3], &sps, &cps);
-  const float tth = tanf(x.v[4]);
-  // body -> world rotation (rotmat)
-  const float R00 = cps * cth, R01 = cps * sth * sph - sps * cph,
-              R02 = cps * sth * cph + sps * sph;
-  const float R10 = sps * cth, R11 = sps * sth * sph + cps * cph,
-              R12 = sps * sth * cph - cps * sph;
-  const float R20 = -sth, R21 = cth * sph, R22 = cth * cph;
-  const float u = x.v[6], v = x.v[7], w = x.v[8];
-  const float p = x.v[11], q = x.v[10], r = x.v[9];
-  const float grav = cst[CF_GRAV];
-  const float Ix = cst[CF_INERTIA], Iy = cst[CF_INERTIA + 1], Iz = cst[CF_INERTIA + 2];
-
-  CfState k;
-  // world-frame velocity
-  k.v[0] = R00 * u + R01 * v + R02 * w;
-  k.v[1] = R10 * u + R11 * v + R12 * w;
-  k.v[2] = R20 * u + R21 * v + R22 * w;
-  // euler rates (psi., theta., phi.) = mat . pqr
-  k.v[3] = (sph / cth) * q + (cph / cth) * r;
-  k.v[4] = cph * q - sph * r;
-  k.v[5] = p + (sph * tth) * q + (cph * tth) * r;
-  // body accel: -pqr x uvw + body-frame gravity
-  k.v[6] = -(q * w - r * v) - R20 * grav;
-  k.v[7] = -(r * u - p * w) - R21 * grav;
-  k.v[8] = -(p * v - q * u) - R22 * grav;
-  // pqr. = -pqr x (I pqr) / I, stored flipped (r, q, p)
-  const float Ip = Ix * p, Iq = Iy * q, Ir = Iz * r;
-  k.v[11] = -(q * Ir - r * Iq) / Ix;
-  k.v[10] = -(r * Ip - p * Ir) / Iy;
-  k.v[9] = -(p * Iq - q * Ip) / Iz;
-
-  // low-level LQR on (phi, theta, psi, p, q, r, v_W) - des
-  float d[9];
-  d[0] = x.v[5];
-  d[1] = x.v[4];
-  d[2] = x.v[3];
-  d[3] = p;
-  d[4] = q;
-  d[5] = r - vt[3];
-  d[6] = k.v[0] - vt[0];
-  d[7] = k.v[1] - vt[1];
-  d[8] = k.v[2] - vt[2];
-  float motor[4];
-#pragma unroll
-  for (int m = 0; m < 4; ++m) {
-    float acc = 0.f;
-#pragma unroll
-    for (int j = 0; j < 9; ++j) acc += cst[CF_KLL + m * 9 + j] * d[j];
-    motor[m] = cst[CF_UEQ + m] - acc;
-  }
-  float wpqr[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    float acc = 0.f;
-#pragma unroll
-    for (int m = 0; m < 4; ++m) acc += cst[CF_MM + i * 4 + m] * motor[m];
-    wpqr[i] = acc;
-  }
-  k.v[8] += wpqr[0];
-  k.v[11] += wpqr[1];
-  k.v[10] += wpqr[2];
-  k.v[9] += wpqr[3];
-  return k;
-}
+// The dynamics (nominal controller, xdot, RK4) live in crazyflie_dyn.h, shared
+// with the loss prologue (loss_prep.hip); this kernel is their float
+// instantiation.
+#include "crazyflie_dyn.h"
 
 __launch_bounds__(256) __global__
 void crazyflie_step_kernel(const float* __restrict__ states,   // (B, V, 12)
@@ -482,7 +410,6 @@ void crazyflie_step_kernel(const float* __restrict__ states,   // (B, V, 12)
   float* nx = next_states + (long)b * V * 12;
   const float comm = cst[CF_COMM];
   const float drone_r = cst[CF_DRONE_R];
-  const float dt = cst[CF_DT];
 
   for (int i = tid; i < K; i += 256) {
     sSph[i * 4 + 0] = centers[((long)b * K + i) * 3 + 0];
@@ -496,58 +423,28 @@ void crazyflie_step_kernel(const float* __restrict__ states,   // (B, V, 12)
     const float* ap = st + (long)i * 12;
     const float* gl = st + (long)(N + i) * 12;
     CfState x;
-    float err[12];
 #pragma unroll
-    for (int s = 0; s < 12; ++s) {
-      x.v[s] = ap[s];
-      err[s] = x.v[s] - gl[s];
-    }
+    for (int s = 0; s < 12; ++s) x.v[s] = ap[s];
     sCur[i * 3 + 0] = x.v[0];
     sCur[i * 3 + 1] = x.v[1];
     sCur[i * 3 + 2] = x.v[2];
     // u_ref: position error rescaled to comm when farther than comm
-    const float dist = sqrtf(err[0] * err[0] + err[1] * err[1] + err[2] * err[2]);
-    const float coef = dist > comm ? comm / fmaxf(dist, 1e-4f) : 1.f;
-    err[0] *= coef;
-    err[1] *= coef;
-    err[2] *= coef;
+    float err[12];
+    crazyflie_goal_err(x, gl, cst, err);
     float vt[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
-      float acc = 0.f;
-#pragma unroll
-      for (int s = 0; s < 12; ++s) acc += cst[CF_KNOM + u * 12 + s] * err[s];
       const float lo = cst[CF_ALO + u], hi = cst[CF_AHI + u];
-      const float uref = fminf(fmaxf(-acc, lo), hi);
+      const float uref = crazyflie_uref(err, u, cst);
       const float av = fminf(fmaxf(action[((long)b * N + i) * 4 + u], lo), hi);
       r_part += (av - uref) * (av - uref);
       vt[u] = av * cst[CF_VTS + u];
     }
     // classic RK4, LL controller re-evaluated per stage
-    const float hdt = 0.5f * dt;
-    CfState k = crazyflie_xdot(x, vt, cst);
-    CfState sum = k, xs;
+    const CfState xn = crazyflie_rk4(x, vt, cst);
 #pragma unroll
-    for (int s = 0; s < 12; ++s) xs.v[s] = x.v[s] + hdt * k.v[s];
-    k = crazyflie_xdot(xs, vt, cst);
-#pragma unroll
-    for (int s = 0; s < 12; ++s) {
-      sum.v[s] += 2.f * k.v[s];
-      xs.v[s] = x.v[s] + hdt * k.v[s];
-    }
-    k = crazyflie_xdot(xs, vt, cst);
-#pragma unroll
-    for (int s = 0; s < 12; ++s) {
-      sum.v[s] += 2.f * k.v[s];
-      xs.v[s] = x.v[s] + dt * k.v[s];
-    }
-    k = crazyflie_xdot(xs, vt, cst);
-    const float dt6 = dt / 6.f;
-#pragma unroll
-    for (int s = 0; s < 12; ++s) {
-      const float xn = x.v[s] + dt6 * (sum.v[s] + k.v[s]);
-      sNext[i * 12 + s] = fminf(fmaxf(xn, cst[CF_SLO + s]), cst[CF_SHI + s]);
-    }
+    for (int s = 0; s < 12; ++s)
+      sNext[i * 12 + s] = fminf(fmaxf(xn.v[s], cst[CF_SLO + s]), cst[CF_SHI + s]);
   }
   __syncthreads();
 

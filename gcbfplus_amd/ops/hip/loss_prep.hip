@@ -5,6 +5,7 @@
 // Replaces ~20 eager kernels per minibatch. Backward chains to actor_raw
 // only (mb states are leaves): dactor = 2 * m_act o (daction +
 // (dt/m) * m_vel o dnext_vel).
+// The CrazyFlie prologue (RK4, dual-number backward) follows further down.
 #include "common.h"
 
 __launch_bounds__(256) __global__
@@ -110,5 +111,125 @@ void di_loss_prep_bwd_kernel(const float* __restrict__ states, const float* __re
       const float dact = daction[it * 2 + u] + dnx[2 + u] * m_vel * inv_m * dt;
       draw[it * 2 + u] = 2.f * m_act * dact;
     }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// CrazyFlie prologue (env/crazyflie.py u_ref + forward_graph):
+//   action = 2*raw + u_ref, stored UNCLAMPED (the action loss sees it so)
+//   next_agent = clip_state(RK4(x, clamp(action) * vel_targets_scale)), the
+//                low-level LQR re-evaluated per stage
+//   big = [ states ; next_states ]
+// The dynamics are crazyflie_dyn.h, shared with the env step kernel: float
+// for the values, CfDual (value + one tangent) for the backward, which
+// recomputes the RK4 with the tangent seeded on one action component, so
+// d x_next / d a[c] covers both df/dx (through the stage states) and df/du.
+//   draw[c] = 2*daction[c] + 2 * m_act[c] * sum_s m_state[s] * dnext[s]
+//             * d x_next[s] / d a[c]
+// m_act / m_state are torch.clamp's inclusive pass-through masks.
+// State and stage vectors are indexed by unrolled constants only (registers).
+// ---------------------------------------------------------------------------
+#include "crazyflie_dyn.h"
+
+__launch_bounds__(256) __global__
+void crazyflie_loss_prep_fwd_kernel(const float* __restrict__ states,  // (B,V,12)
+                                    const float* __restrict__ raw,     // (B,N,4)
+                                    const float* __restrict__ cst,     // (CF_NCONST,)
+                                    float* __restrict__ action,        // (B,N,4)
+                                    float* __restrict__ big,           // (2B,V,12)
+                                    int B, int V, int N) {
+  const long rows = (long)2 * B * V;
+  for (long row = (long)blockIdx.x * blockDim.x + threadIdx.x; row < rows;
+       row += (long)gridDim.x * blockDim.x) {
+    const int v = row % V;
+    const long bb = row / V;
+    const int half = bb / B;     // 0: current, 1: next
+    const int b = bb % B;
+    const float4* src = (const float4*)(states + ((long)b * V + v) * 12);
+    float4* dst = (float4*)(big + row * 12);
+    const float4 s0 = src[0], s1 = src[1], s2 = src[2];
+    if (half == 0 || v >= N) {
+      dst[0] = s0;
+      dst[1] = s1;
+      dst[2] = s2;
+      continue;
+    }
+    // next agent state for agent i = v
+    const int i = v;
+    CfState x;
+    x.v[0] = s0.x, x.v[1] = s0.y, x.v[2] = s0.z, x.v[3] = s0.w;
+    x.v[4] = s1.x, x.v[5] = s1.y, x.v[6] = s1.z, x.v[7] = s1.w;
+    x.v[8] = s2.x, x.v[9] = s2.y, x.v[10] = s2.z, x.v[11] = s2.w;
+    float err[12];
+    crazyflie_goal_err(x, states + ((long)b * V + N + i) * 12, cst, err);
+    const float4 rw = *(const float4*)(raw + ((long)b * N + i) * 4);
+    const float r4[4] = {rw.x, rw.y, rw.z, rw.w};
+    float act[4], vt[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      act[u] = 2.f * r4[u] + crazyflie_uref(err, u, cst);
+      vt[u] = fminf(fmaxf(act[u], cst[CF_ALO + u]), cst[CF_AHI + u]) * cst[CF_VTS + u];
+    }
+    *(float4*)(action + ((long)b * N + i) * 4) = make_float4(act[0], act[1], act[2], act[3]);
+    const CfState xn = crazyflie_rk4(x, vt, cst);
+    float o[12];
+#pragma unroll
+    for (int s = 0; s < 12; ++s)
+      o[s] = fminf(fmaxf(xn.v[s], cst[CF_SLO + s]), cst[CF_SHI + s]);
+    dst[0] = make_float4(o[0], o[1], o[2], o[3]);
+    dst[1] = make_float4(o[4], o[5], o[6], o[7]);
+    dst[2] = make_float4(o[8], o[9], o[10], o[11]);
+  }
+}
+
+// one thread per (b, i, c): the dual RK4 seeded on action component c
+__launch_bounds__(256) __global__
+void crazyflie_loss_prep_bwd_kernel(const float* __restrict__ states,   // (B,V,12)
+                                    const float* __restrict__ cst,      // (CF_NCONST,)
+                                    const float* __restrict__ action,   // (B,N,4) unclamped
+                                    const float* __restrict__ daction,  // (B,N,4)
+                                    const float* __restrict__ dbig,     // (2B,V,12)
+                                    float* __restrict__ draw,           // (B,N,4)
+                                    int B, int V, int N) {
+  const long total = (long)B * N * 4;
+  for (long it = (long)blockIdx.x * blockDim.x + threadIdx.x; it < total;
+       it += (long)gridDim.x * blockDim.x) {
+    const int c = it & 3;
+    const long ag = it >> 2;  // b * N + i
+    const int i = ag % N;
+    const long b = ag / N;
+    const float4 aw = *(const float4*)(action + ag * 4);
+    const float a4[4] = {aw.x, aw.y, aw.z, aw.w};
+    const float pre = action[it];
+    const float two_da = 2.f * daction[it];
+    if (!(pre >= cst[CF_ALO + c] && pre <= cst[CF_AHI + c])) {
+      draw[it] = two_da;  // clamp active: nothing flows from the dynamics
+      continue;
+    }
+    const float4* src = (const float4*)(states + (b * V + i) * 12);
+    const float4 s0 = src[0], s1 = src[1], s2 = src[2];
+    CfStateT<CfDual> x;
+    x.v[0] = s0.x, x.v[1] = s0.y, x.v[2] = s0.z, x.v[3] = s0.w;
+    x.v[4] = s1.x, x.v[5] = s1.y, x.v[6] = s1.z, x.v[7] = s1.w;
+    x.v[8] = s2.x, x.v[9] = s2.y, x.v[10] = s2.z, x.v[11] = s2.w;
+    CfDual vt[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const float scale = cst[CF_VTS + u];
+      vt[u] = CfDual(fminf(fmaxf(a4[u], cst[CF_ALO + u]), cst[CF_AHI + u]) * scale,
+                     u == c ? scale : 0.f);
+    }
+    const CfStateT<CfDual> xn = crazyflie_rk4(x, vt, cst);
+    const float4* dn = (const float4*)(dbig + ((B + b) * V + i) * 12);
+    const float4 d0 = dn[0], d1 = dn[1], d2 = dn[2];
+    const float g[12] = {d0.x, d0.y, d0.z, d0.w, d1.x, d1.y,
+                         d1.z, d1.w, d2.x, d2.y, d2.z, d2.w};
+    float acc = 0.f;
+#pragma unroll
+    for (int s = 0; s < 12; ++s) {
+      const bool pass = xn.v[s].v >= cst[CF_SLO + s] && xn.v[s].v <= cst[CF_SHI + s];
+      acc += pass ? g[s] * xn.v[s].d : 0.f;
+    }
+    draw[it] = two_da + 2.f * acc;
   }
 }
