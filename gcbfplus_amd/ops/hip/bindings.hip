@@ -668,6 +668,27 @@ torch::Tensor fused_adamw_step(torch::Tensor p, torch::Tensor g, torch::Tensor m
   return norm;
 }
 
+// K11 dispatch. ONE host function maps (nv, k) to the proxqp_kernel
+// instantiation; the launcher, the launch-free `proxqp_path` query and the
+// Python gate in ops/qp.py all go through it, so the limits cannot drift and
+// a test can assert the path a shape takes.
+enum ProxqpPath { PQ_NONE, PQ_W32X16, PQ_W64X32 };
+
+static ProxqpPath proxqp_plan(long nv, long k) {
+  if (nv < 1 || k < 0) return PQ_NONE;
+  if (nv <= 32 && k <= 16) return PQ_W32X16;
+  if (nv <= 64 && k <= 32) return PQ_W64X32;
+  return PQ_NONE;  // caller takes the torch float64 path
+}
+
+std::string proxqp_path(long nv, long k) {
+  switch (proxqp_plan(nv, k)) {
+    case PQ_W32X16: return "w32x16";
+    case PQ_W64X32: return "w64x32";
+    default: return "none";
+  }
+}
+
 torch::Tensor proxqp_solve_hip(torch::Tensor H, torch::Tensor g, torch::Tensor C,
                                torch::Tensor b, torch::Tensor l, torch::Tensor u,
                                long iters, double rho, double sigma, double alpha) {
@@ -677,23 +698,31 @@ torch::Tensor proxqp_solve_hip(torch::Tensor H, torch::Tensor g, torch::Tensor C
   CHECK_IN(b);
   CHECK_IN(l);
   CHECK_IN(u);
+  TORCH_CHECK(g.dim() == 2 && b.dim() == 2, "proxqp_solve_hip: g must be (M, nv), b (M, k)");
   long M = g.size(0), nv = g.size(1), k = b.size(1);
+  TORCH_CHECK(H.numel() == M * nv * nv && C.numel() == M * k * nv && b.size(0) == M &&
+                  l.numel() == M * nv && u.numel() == M * nv,
+              "proxqp_solve_hip: operand shapes do not match M=", M, " nv=", nv, " k=", k);
+  const ProxqpPath path = proxqp_plan(nv, k);
+  TORCH_CHECK(path != PQ_NONE, "proxqp_solve_hip: nv=", nv, " k=", k,
+              " too large for the kernel path");
   auto x = torch::empty({M, nv}, g.options());
+  if (M == 0) return x;
   auto stream = cur_stream();
-  if (nv <= 32 && k <= 16) {
+  if (path == PQ_W32X16) {
     hipLaunchKernelGGL((proxqp_kernel<32, 16>), dim3(M), dim3(64), 0, stream,
                        H.data_ptr<float>(), g.data_ptr<float>(), C.data_ptr<float>(),
                        b.data_ptr<float>(), l.data_ptr<float>(), u.data_ptr<float>(),
                        x.data_ptr<float>(), (int)M, (int)nv, (int)k, (int)iters,
                        (float)rho, (float)sigma, (float)alpha);
-  } else if (nv <= 64 && k <= 32) {
+    C10_HIP_KERNEL_LAUNCH_CHECK();
+  } else {
     hipLaunchKernelGGL((proxqp_kernel<64, 32>), dim3(M), dim3(64), 0, stream,
                        H.data_ptr<float>(), g.data_ptr<float>(), C.data_ptr<float>(),
                        b.data_ptr<float>(), l.data_ptr<float>(), u.data_ptr<float>(),
                        x.data_ptr<float>(), (int)M, (int)nv, (int)k, (int)iters,
                        (float)rho, (float)sigma, (float)alpha);
-  } else {
-    TORCH_CHECK(false, "proxqp_solve_hip: nv/k too large for the kernel path");
+    C10_HIP_KERNEL_LAUNCH_CHECK();
   }
   return x;
 }
@@ -1023,6 +1052,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fused_adamw_step", &fused_adamw_step,
         "flat-buffer global-norm-clip AdamW with finite guard (K13)");
   m.def("proxqp_solve", &proxqp_solve_hip, "batched dense QP, one wave per problem (K11)");
+  m.def("proxqp_path", &proxqp_path,
+        "proxqp_kernel instantiation for (nv, k): w32x16 | w64x32 | none (torch path)");
   m.def("gemm_bias_act", &gemm_bias_act, "Y = act(X@W + b), MFMA bf16");
   m.def("gemm_path", &gemm_path, "kernel a GEMM-family op selects for a shape (no launch)",
         py::arg("op"), py::arg("M"), py::arg("K"), py::arg("N"), py::arg("actin") = 0,

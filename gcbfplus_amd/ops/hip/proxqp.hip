@@ -2,10 +2,17 @@
 //
 //   min 1/2 x^T H x + g^T x   s.t.  C x <= b,  l <= x <= u
 //
-// Mirrors the torch oracle (gcbfplus_amd/ops/qp.py) step for step: Ruiz
-// equilibration + cost scaling, ADMM with over-relaxation and OSQP-style
-// adaptive rho (re-factor every 25 iters), then an iterated f64 active-set
-// penalty polish with multiplier-sign release. Fixed iteration count
+// Follows the torch oracle (gcbfplus_amd/ops/qp.py): Ruiz equilibration +
+// cost scaling, ADMM with over-relaxation and OSQP-style adaptive rho
+// (re-factor every 25 iters), then an iterated f64 active-set penalty polish
+// with multiplier-sign release. Two known differences in the polish
+// (profiles/qp_accuracy.md): the oracle adds a 1e-8 ridge to the system, the
+// kernel clamps Cholesky pivots at 1e-18; the oracle releases a pinned row
+// only if the candidate sits at exactly one of its bounds, the kernel codes
+// every pinned row as hi or lo and so also releases rows pinned through the
+// ADMM dual alone. ADMM in float32, as the oracle's host path (its device
+// fallback runs float64); tests/test_qp_paths_gpu.py judges both against a
+// certified float64 optimum on every dispatch path. Fixed iteration count
 // (JaxProxQP-style batched semantics, reference gcbf_plus.py:341-346).
 //
 // The per-iteration KKT solve uses an explicit K^{-1} = L^{-T} L^{-1}

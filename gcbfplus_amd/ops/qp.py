@@ -25,6 +25,14 @@ import torch
 from torch import Tensor
 
 
+def kernel_path(nv: int, k: int) -> str:
+    """HIP kernel instantiation a GPU solve of (nv variables, k rows) takes:
+    "w32x16", "w64x32", or "none" for the torch float64 fallback."""
+    from . import _require_ext
+
+    return _require_ext().proxqp_path(nv, k)
+
+
 def proxqp_solve(
     H: Tensor,  # (M, n, n)
     g: Tensor,  # (M, n)
@@ -48,7 +56,9 @@ def proxqp_solve(
     CPU oracle and the large-problem fallback.
     """
     M, n = g.shape
-    if g.is_cuda and n <= 64 and b.shape[1] <= 32:
+    # the kernel's size limits live in ONE host function of the extension
+    # (bindings.hip proxqp_plan); "none" means the torch path below
+    if g.is_cuda and kernel_path(n, b.shape[1]) != "none":
         from . import _require_ext
 
         ext = _require_ext()
