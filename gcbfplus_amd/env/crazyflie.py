@@ -33,19 +33,7 @@ X, Y, Z, PSI, THETA, PHI, U, V, W, R_, Q_, P_ = range(12)
 GRAVITY = 9.81
 
 
-def rotmat(phi: Tensor, theta: Tensor, psi: Tensor) -> Tensor:
-    """(...,) angles -> (..., 3, 3) body->world rotation (reference :19-33)."""
-    c_phi, s_phi = torch.cos(phi), torch.sin(phi)
-    c_th, s_th = torch.cos(theta), torch.sin(theta)
-    c_psi, s_psi = torch.cos(psi), torch.sin(psi)
-    rows = [
-        torch.stack([c_psi * c_th, c_psi * s_th * s_phi - s_psi * c_phi,
-                     c_psi * s_th * c_phi + s_psi * s_phi], dim=-1),
-        torch.stack([s_psi * c_th, s_psi * s_th * s_phi + c_psi * c_phi,
-                     s_psi * s_th * c_phi - c_psi * s_phi], dim=-1),
-        torch.stack([-s_th, c_th * s_phi, c_th * c_phi], dim=-1),
-    ]
-    return torch.stack(rows, dim=-2)
+rotmat = ops.crazyflie_rotmat  # (...,) angles -> (..., 3, 3) body->world rotation
 
 
 class CrazyFlie(LinearDrone):
@@ -64,8 +52,15 @@ class CrazyFlie(LinearDrone):
         "d": 0.03973,
     }
 
-    fused_edge = False
     analytic_edge_jac = True  # single-backward fast path (edge_grad_to_state_jac)
+
+    @property
+    def fused_edge(self) -> bool:
+        """ops.edge_msg_in (mode 2) and ops.crazyflie_edge_jac cover this env:
+        only the exact class (subclasses may override ``_edge_states``) on a
+        GPU with the extension. GCBF_NO_FUSED_EDGE forces the torch path."""
+        return (type(self) is CrazyFlie and self.device.type == "cuda"
+                and ops.hip_available() and not os.environ.get("GCBF_NO_FUSED_EDGE"))
 
     def __init__(self, num_agents, area_size, max_step=256, max_travel=None, dt=0.03,
                  params=None, device=None):
@@ -357,11 +352,7 @@ class CrazyFlie(LinearDrone):
     def _edge_states(self, states: Tensor) -> Tensor:
         """12-dim world-frame edge state: [pos, vel_W, z-axis_W, omega_W]
         (reference edge_state, :165-182)."""
-        Rm = rotmat(states[..., PHI], states[..., THETA], states[..., PSI])
-        v_W = torch.einsum("...ij,...j->...i", Rm, states[..., U : W + 1])
-        z_W = Rm[..., :, 2]
-        omega_W = torch.einsum("...ij,...j->...i", Rm, states[..., R_ : P_ + 1].flip(-1))
-        return torch.cat([states[..., :3], v_W, z_W, omega_W], dim=-1)
+        return ops.crazyflie_edge_states(states)
 
     def edge_grad_to_state_jac(self, graph: GraphBatch, states: Tensor, ge: Tensor) -> Tensor:
         """Chain dh/d(edge_feats) -> dh_i/dx_j (M, N, N, 12) analytically:
@@ -372,6 +363,10 @@ class CrazyFlie(LinearDrone):
         torch.func.jacrev. Replaces N reverse passes through the whole GNN
         (reference gcbf_plus.py:310-317) with ONE backward + one tiny
         batched jacobian."""
+        if self.fused_edge and states.is_cuda:
+            # the same computation in one HIP kernel after a node pre-pass
+            return ops.crazyflie_edge_jac(states, ge, self.num_agents, self.n_rays,
+                                          self._params["comm_radius"])
         import torch.func as tf
 
         M, N, D, E = ge.shape
@@ -403,6 +398,14 @@ class CrazyFlie(LinearDrone):
         JT = tf.vmap(tf.jacrev(self._edge_states))(agent)  # (M*N, 12, 12)
         JT = JT.reshape(M, N, E, self.state_dim)
         return torch.einsum("mije,mjes->mijs", h_es, JT)
+
+    def edge_msg_in(self, graph: GraphBatch, states: Optional[Tensor] = None) -> Tensor:
+        """Fused layer-0 GNN input (ops.edge_msg_in mode 2): the edge features
+        below with both one-hots, (B, N, D, 32)."""
+        if states is None:
+            states = graph.states
+        return ops.edge_msg_in(states, self.num_agents, self.n_rays, 3,
+                               self._params["comm_radius"], mode=2)
 
     def edge_feats(self, graph: GraphBatch, states: Optional[Tensor] = None) -> Tensor:
         if states is None:

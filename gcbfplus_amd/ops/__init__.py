@@ -14,7 +14,9 @@ Op inventory (kernel numbering follows SURVEY.md §2.7):
                       (backward: transposed-B dX, deterministic split-M dW,
                       upstream-activation fold, direct grad accumulation)
   masked_softmax_aggr K3/K4: per-receiver masked softmax + weighted message sum
-  edge_msg_in         K2/K15: fused layer-0 GNN input build (+ analytic bwd)
+  edge_msg_in         K2/K15: fused layer-0 GNN input build (+ analytic bwd);
+                      mode 0 state diff, 1 DubinsCar, 2 CrazyFlie (node pre-pass)
+  crazyflie_edge_jac  dh/d(edge feats) -> dh_i/dx_j for the CrazyFlie QP labels
   raytrace_rect       K1: 2D LiDAR fan vs rectangle set (no grad)
   gcbf_plus_loss      K10: all GCBF+ hinge losses + metrics in one kernel pair
   di_loss_prep        K10 prologue: u_ref + action clamp + euler + [cur; next]
@@ -350,14 +352,50 @@ class _EdgeMsgInHIP(torch.autograd.Function):
         return dstates, None, None, None, None, None, None
 
 
+def crazyflie_rotmat(phi: Tensor, theta: Tensor, psi: Tensor) -> Tensor:
+    """(...,) angles -> (..., 3, 3) body->world rotation (reference
+    env/crazyflie.py:19-33). Lives here, not in env/crazyflie.py (which
+    re-exports it as ``rotmat``), because env imports ops."""
+    c_phi, s_phi = torch.cos(phi), torch.sin(phi)
+    c_th, s_th = torch.cos(theta), torch.sin(theta)
+    c_psi, s_psi = torch.cos(psi), torch.sin(psi)
+    rows = [
+        torch.stack([c_psi * c_th, c_psi * s_th * s_phi - s_psi * c_phi,
+                     c_psi * s_th * c_phi + s_psi * s_phi], dim=-1),
+        torch.stack([s_psi * c_th, s_psi * s_th * s_phi + c_psi * c_phi,
+                     s_psi * s_th * c_phi - c_psi * s_phi], dim=-1),
+        torch.stack([-s_th, c_th * s_phi, c_th * c_phi], dim=-1),
+    ]
+    return torch.stack(rows, dim=-2)
+
+
+def crazyflie_edge_states(states: Tensor) -> Tensor:
+    """12-dim world-frame edge state [pos, vel_W, z-axis_W, omega_W] of
+    (..., 12) states (x,y,z, psi,theta,phi, u,v,w, r,q,p) (reference
+    edge_state, env/crazyflie.py:165-182): the torch definition behind
+    ``CrazyFlie._edge_states`` and the CPU path of ``edge_msg_in`` mode 2."""
+    Rm = crazyflie_rotmat(states[..., 5], states[..., 4], states[..., 3])
+    v_W = torch.einsum("...ij,...j->...i", Rm, states[..., 6:9])
+    z_W = Rm[..., :, 2]
+    omega_W = torch.einsum("...ij,...j->...i", Rm, states[..., 9:12].flip(-1))
+    return torch.cat([states[..., :3], v_W, z_W, omega_W], dim=-1)
+
+
 def edge_msg_in(states: Tensor, n_agents: int, n_rays: int, pos_dim: int,
                 comm: float, k_pad: Optional[int] = None, mode: int = 0) -> Tensor:
     """Fused layer-0 GNN input: per edge slot
-    [clip(recv - send) | sender one-hot | recv one-hot | 0 pad], (B, N, D, KP).
+    [clip(es_recv - es_send) | sender one-hot | recv one-hot | 0 pad],
+    (B, N, D, KP), where es is the edge state of a node:
 
-    Valid for the 'state-diff + position-clip' edge-feature family
-    (SI/DI/LinearDrone; reference double_integrator.py:275-286 + one-hot
-    node feats :288-295). GPU: bf16 kernel pair; CPU: composed fp32 torch.
+      mode 0  es = state (SI/DI/LinearDrone; reference
+              double_integrator.py:275-286 + one-hot node feats :288-295)
+      mode 1  DubinsCar [x, y, v cos(theta), v sin(theta)]
+      mode 2  CrazyFlie [pos, R uvw, R[:, 2], R pqr] on every node (S = 12,
+              pos_dim = 3, KP = 32); the trigonometry runs once per node in a
+              pre-pass, forward and backward
+
+    GPU: bf16 kernel pair (the extension refuses any other mode, and shapes
+    mode 2 does not cover); CPU: composed fp32 torch, differentiable.
     """
     B, V, S = states.shape
     K = S + 6
@@ -365,12 +403,18 @@ def edge_msg_in(states: Tensor, n_agents: int, n_rays: int, pos_dim: int,
         k_pad = (K + 31) // 32 * 32
     if states.is_cuda:
         return _EdgeMsgInHIP.apply(states, n_agents, n_rays, pos_dim, k_pad, comm, mode)
+    if mode not in (0, 1, 2):
+        raise ValueError(f"edge_msg_in: unknown mode {mode}")
     # CPU compose (fp32)
     if mode == 1:  # DubinsCar edge-state transform [x, y, v cos, v sin]
         th, v = states[..., 2], states[..., 3]
         states = torch.stack(
             [states[..., 0], states[..., 1], v * torch.cos(th), v * torch.sin(th)], dim=-1
         )
+    elif mode == 2:
+        if S != 12 or pos_dim != 3:
+            raise ValueError("edge_msg_in mode 2 needs S == 12 and pos_dim == 3")
+        states = crazyflie_edge_states(states)
     n, r = n_agents, n_rays
     recv = states[:, :n, None, :]
     senders = torch.cat(
@@ -396,6 +440,19 @@ def edge_msg_in(states: Tensor, n_agents: int, n_rays: int, pos_dim: int,
     if k_pad > K:
         out = torch.cat([out, out.new_zeros(B, n, D, k_pad - K)], dim=-1)
     return out
+
+
+def crazyflie_edge_jac(states: Tensor, ge: Tensor, n_agents: int, n_rays: int,
+                       comm: float) -> Tensor:
+    """Fused ``CrazyFlie.edge_grad_to_state_jac``: states (M, V, 12) and
+    ge (M, N, D, 12) f32 = dh/d(edge feats) -> h_x (M, N, N, 12) = dh_i/dx_j
+    (clip vjp per slot, receiver-side sum on the diagonal, transposed
+    edge-state jacobian of agent j). GPU only (node pre-pass + one kernel, no
+    grad); CPU callers take the torch body in env/crazyflie.py."""
+    if not states.is_cuda:
+        raise NotImplementedError("CPU path is CrazyFlie.edge_grad_to_state_jac's torch body")
+    return _require_ext().crazyflie_edge_jac(
+        states.detach().contiguous(), ge.detach().float().contiguous(), n_agents, n_rays, comm)
 
 
 # --------------------------------------------------------------------------

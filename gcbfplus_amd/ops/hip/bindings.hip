@@ -4,6 +4,7 @@
 #include <c10/hip/HIPException.h>
 #include <c10/hip/HIPStream.h>
 
+#include <algorithm>
 #include <climits>
 #include <cstdint>
 
@@ -54,6 +55,10 @@ __global__ void edge_msg_in_fwd_kernel(const float*, bf16_t_*, int, int, int, in
 __global__ void edge_msg_in_fwd_s4_kernel(const float*, bf16_t_*, int, int, int, float);
 __global__ void edge_msg_in_bwd_s4_kernel(const float*, const bf16_t_*, float*, int, int, int, float);
 __global__ void edge_msg_in_bwd_kernel(const float*, const bf16_t_*, float*, int, int, int, int, int, int, float, int);
+__global__ void crazyflie_edge_state_kernel(const float*, float*, long);
+__global__ void edge_msg_in_fwd_cf_kernel(const float*, bf16_t_*, int, int, int, float);
+__global__ void edge_msg_in_bwd_cf_kernel(const float*, const float*, const bf16_t_*, float*, int, int, int, float);
+__global__ void crazyflie_edge_jac_kernel(const float*, const float*, const float*, float*, int, int, int, float);
 __global__ void gcbf_loss_fwd_kernel(const float*, const float*, const float*, const float*, const float*, const bool*, const bool*, float*, long, int, float, float, float, float, float, float, float);
 __global__ void di_loss_prep_fwd_kernel(const float*, const float*, const float*, float*, float*,
                                         int, int, int, float, float, float, float);
@@ -727,8 +732,59 @@ torch::Tensor proxqp_solve_hip(torch::Tensor H, torch::Tensor g, torch::Tensor C
   return x;
 }
 
+// grid of a grid-stride kernel over `total` items, 256 threads per block
+static inline dim3 edge_grid(long total) {
+  return dim3((unsigned)std::min<long>(std::max<long>((total + 255) / 256, 1), 1L << 20));
+}
+
+// the CrazyFlie kernels read 48 B / 64 B rows with b128 accesses
+static inline bool b128_aligned(const torch::Tensor& t) {
+  return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
+}
+
+// mode 2 (CrazyFlie) operand contract, checked before any launch
+static void check_crazyflie_edge(const torch::Tensor& states, long N, long R,
+                                 const char* who) {
+  TORCH_CHECK(states.is_cuda() && states.is_contiguous() &&
+                  states.scalar_type() == torch::kFloat32 && states.dim() == 3,
+              who, ": states must be a contiguous f32 (B, V, 12) GPU tensor");
+  TORCH_CHECK(states.size(2) == 12, who, ": CrazyFlie states have S == 12, got ",
+              states.size(2));
+  TORCH_CHECK(b128_aligned(states), who, ": states must be 16 B aligned");
+  TORCH_CHECK(N >= 1 && R >= 0 && states.size(1) == 2 * N + N * R, who, ": V = ",
+              states.size(1), " is not 2N + N*R for N = ", N, ", R = ", R);
+}
+
+// node pre-pass: es = edge-state transform of every node, f32 (B, V, 12).
+// Allocated through torch on the current stream (capture-safe).
+static torch::Tensor crazyflie_edge_states(const torch::Tensor& states) {
+  auto es = torch::empty_like(states);
+  long nodes = states.size(0) * states.size(1);
+  if (nodes == 0) return es;
+  hipLaunchKernelGGL(crazyflie_edge_state_kernel, edge_grid(nodes), dim3(256), 0,
+                     cur_stream(), states.data_ptr<float>(), es.data_ptr<float>(), nodes);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return es;
+}
+
 torch::Tensor edge_msg_in_fwd(torch::Tensor states, long N, long R, long pdim, long KP,
                               double comm, long mode) {
+  TORCH_CHECK(mode >= 0 && mode <= 2, "edge_msg_in_fwd: unknown mode ", mode);
+  if (mode == 2) {
+    check_crazyflie_edge(states, N, R, "edge_msg_in_fwd(mode 2)");
+    TORCH_CHECK(pdim == 3 && KP == 32, "edge_msg_in_fwd(mode 2): needs pdim == 3 and KP == 32,"
+                " got pdim = ", pdim, ", KP = ", KP);
+    long B = states.size(0), D = N + 1 + R;
+    auto X = torch::empty({B, N, D, KP}, states.options().dtype(torch::kBFloat16));
+    long total = B * N * D;
+    if (total == 0) return X;
+    auto es = crazyflie_edge_states(states);
+    hipLaunchKernelGGL(edge_msg_in_fwd_cf_kernel, edge_grid(total), dim3(256), 0,
+                       cur_stream(), es.data_ptr<float>(), bfp_mut(X), (int)B, (int)N, (int)R,
+                       (float)comm);
+    C10_HIP_KERNEL_LAUNCH_CHECK();
+    return X;
+  }
   CHECK_IN(states);
   long B = states.size(0), V = states.size(1), S = states.size(2);
   long D = N + 1 + R;
@@ -739,16 +795,37 @@ torch::Tensor edge_msg_in_fwd(torch::Tensor states, long N, long R, long pdim, l
     hipLaunchKernelGGL(edge_msg_in_fwd_s4_kernel, dim3((total + 255) / 256), dim3(256), 0,
                        cur_stream(), states.data_ptr<float>(), bfp_mut(X), (int)B, (int)N,
                        (int)R, (float)comm);
+    C10_HIP_KERNEL_LAUNCH_CHECK();
     return X;
   }
   hipLaunchKernelGGL(edge_msg_in_fwd_kernel, dim3((total + 255) / 256), dim3(256), 0,
                      cur_stream(), states.data_ptr<float>(), bfp_mut(X), (int)B, (int)N,
                      (int)R, (int)S, (int)pdim, (int)KP, (float)comm, (int)mode);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return X;
 }
 
 torch::Tensor edge_msg_in_bwd(torch::Tensor states, torch::Tensor dX, long N, long R,
                               long pdim, double comm, long mode) {
+  TORCH_CHECK(mode >= 0 && mode <= 2, "edge_msg_in_bwd: unknown mode ", mode);
+  if (mode == 2) {
+    check_crazyflie_edge(states, N, R, "edge_msg_in_bwd(mode 2)");
+    long B = states.size(0), V = states.size(1), D = N + 1 + R;
+    TORCH_CHECK(pdim == 3, "edge_msg_in_bwd(mode 2): needs pdim == 3, got ", pdim);
+    TORCH_CHECK(dX.is_cuda() && dX.is_contiguous() && dX.scalar_type() == torch::kBFloat16 &&
+                    dX.dim() == 4 && dX.size(0) == B && dX.size(1) == N && dX.size(2) == D &&
+                    dX.size(3) == 32 && b128_aligned(dX),
+                "edge_msg_in_bwd(mode 2): dX must be a contiguous bf16 (B, N, D, 32) GPU "
+                "tensor matching the states");
+    auto dstates = torch::empty_like(states);
+    if (B * V == 0) return dstates;
+    auto es = crazyflie_edge_states(states);
+    hipLaunchKernelGGL(edge_msg_in_bwd_cf_kernel, edge_grid(B * V), dim3(256), 0,
+                       cur_stream(), states.data_ptr<float>(), es.data_ptr<float>(), bfp(dX),
+                       dstates.data_ptr<float>(), (int)B, (int)N, (int)R, (float)comm);
+    C10_HIP_KERNEL_LAUNCH_CHECK();
+    return dstates;
+  }
   CHECK_IN(states);
   CHECK_IN(dX);
   long B = states.size(0), V = states.size(1), S = states.size(2);
@@ -759,13 +836,36 @@ torch::Tensor edge_msg_in_bwd(torch::Tensor states, torch::Tensor dX, long N, lo
     hipLaunchKernelGGL(edge_msg_in_bwd_s4_kernel, dim3((total + 255) / 256), dim3(256), 0,
                        cur_stream(), states.data_ptr<float>(), bfp(dX),
                        dstates.data_ptr<float>(), (int)B, (int)N, (int)R, (float)comm);
+    C10_HIP_KERNEL_LAUNCH_CHECK();
     return dstates;
   }
   hipLaunchKernelGGL(edge_msg_in_bwd_kernel, dim3((total + 255) / 256), dim3(256), 0,
                      cur_stream(), states.data_ptr<float>(), bfp(dX),
                      dstates.data_ptr<float>(), (int)B, (int)N, (int)R, (int)S, (int)pdim,
                      (int)KP, (float)comm, (int)mode);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return dstates;
+}
+
+// h_x (M, N, N, 12) = dh_i / dx_j from ge (M, N, D, 12) = dh / d(edge feats)
+torch::Tensor crazyflie_edge_jac(torch::Tensor states, torch::Tensor ge, long N, long R,
+                                 double comm) {
+  check_crazyflie_edge(states, N, R, "crazyflie_edge_jac");
+  long M = states.size(0), D = N + 1 + R;
+  TORCH_CHECK(ge.is_cuda() && ge.is_contiguous() && ge.scalar_type() == torch::kFloat32 &&
+                  ge.dim() == 4 && ge.size(0) == M && ge.size(1) == N && ge.size(2) == D &&
+                  ge.size(3) == 12 && b128_aligned(ge),
+              "crazyflie_edge_jac: ge must be a contiguous f32 (M, N, D, 12) GPU tensor "
+              "matching the states");
+  auto hx = torch::empty({M, N, N, 12}, states.options());
+  if (M == 0) return hx;
+  auto es = crazyflie_edge_states(states);
+  hipLaunchKernelGGL(crazyflie_edge_jac_kernel, edge_grid(M * N * N), dim3(256), 0,
+                     cur_stream(), states.data_ptr<float>(), es.data_ptr<float>(),
+                     ge.data_ptr<float>(), hx.data_ptr<float>(), (int)M, (int)N, (int)R,
+                     (float)comm);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return hx;
 }
 
 torch::Tensor gcbf_loss_fwd(torch::Tensor h, torch::Tensor h_next, torch::Tensor h_ng,
@@ -1049,6 +1149,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gcbf_loss_bwd", &gcbf_loss_bwd);
   m.def("edge_msg_in_fwd", &edge_msg_in_fwd);
   m.def("edge_msg_in_bwd", &edge_msg_in_bwd);
+  m.def("crazyflie_edge_jac", &crazyflie_edge_jac);
   m.def("fused_adamw_step", &fused_adamw_step,
         "flat-buffer global-norm-clip AdamW with finite guard (K13)");
   m.def("proxqp_solve", &proxqp_solve_hip, "batched dense QP, one wave per problem (K11)");

@@ -11,6 +11,10 @@
 // bwd: dX -> dstates via the clip-jacobian vjp, ATOMIC-FREE: each node
 // gathers its fixed contribution set (receiver side: own row; sender side:
 // slots that point at it) in a deterministic order.
+//
+// The edge state of a node is its state (mode 0), the DubinsCar transform
+// (mode 1, re-evaluated per slot) or the CrazyFlie transform (mode 2, end of
+// this file: evaluated once per node in a pre-pass).
 #include "common.h"
 
 // slot layout: d in [0,N) sender=agent d | d==N sender=goal i | else lidar
@@ -279,5 +283,192 @@ void edge_msg_in_bwd_kernel(const float* __restrict__ states, const bf16_t* __re
     } else {
       for (int s = 0; s < S; ++s) out[s] = acc[s];
     }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// mode 2: CrazyFlie. S = 12, pdim = 3, KP = 32. The edge state is the
+// rotation-matrix transform of crazyflie_edge.h; its six sin/cos run ONCE per
+// node in a pre-pass into an f32 (B,V,12) scratch, and the slot kernels read
+// that scratch (the generic mode-1 path re-evaluates the sender's transform
+// in every slot, which does not scale to D ~ N swarm graphs).
+// ---------------------------------------------------------------------------
+#include "crazyflie_edge.h"
+
+__launch_bounds__(256) __global__
+void crazyflie_edge_state_kernel(const float* __restrict__ states, float* __restrict__ es,
+                                 long n_nodes) {
+  for (long node = (long)blockIdx.x * blockDim.x + threadIdx.x; node < n_nodes;
+       node += (long)gridDim.x * blockDim.x) {
+    float st[12], e[12];
+    cf_load12(states + node * 12, st);
+    cf_edge_state(st, e);
+    cf_store12(es + node * 12, e);
+  }
+}
+
+__launch_bounds__(256) __global__
+void edge_msg_in_fwd_cf_kernel(const float* __restrict__ es, bf16_t* __restrict__ X, int B,
+                               int N, int R, float comm) {
+  const int D = N + 1 + R;
+  const int V = 2 * N + N * R;
+  const long total = (long)B * N * D;
+  for (long row = (long)blockIdx.x * blockDim.x + threadIdx.x; row < total;
+       row += (long)gridDim.x * blockDim.x) {
+    const int d = row % D;
+    const int i = (row / D) % N;
+    const long b = row / ((long)N * D);
+    float er[12], se[12], e[12];
+    cf_load12(es + (b * V + i) * 12, er);
+    cf_load12(es + (b * V + sender_node(i, d, N, R)) * 12, se);
+#pragma unroll
+    for (int s = 0; s < 12; ++s) e[s] = er[s] - se[s];
+    const float n = sqrtf(1e-6f + e[0] * e[0] + e[1] * e[1] + e[2] * e[2]);
+    const float coef = (n > comm) ? comm / n : 1.f;
+    const int stype = (d < N) ? 0 : (d == N ? 1 : 2);
+    bf16x8 o0, o1, o2;
+    o0[0] = (bf16_t)(e[0] * coef);
+    o0[1] = (bf16_t)(e[1] * coef);
+    o0[2] = (bf16_t)(e[2] * coef);
+#pragma unroll
+    for (int s = 3; s < 8; ++s) o0[s] = (bf16_t)e[s];
+#pragma unroll
+    for (int s = 8; s < 12; ++s) o1[s - 8] = (bf16_t)e[s];
+    o1[4] = (bf16_t)(stype == 2 ? 1.f : 0.f);
+    o1[5] = (bf16_t)(stype == 1 ? 1.f : 0.f);
+    o1[6] = (bf16_t)(stype == 0 ? 1.f : 0.f);
+    o1[7] = (bf16_t)0.f;  // recv one-hot: always agent = 001
+    o2[0] = (bf16_t)0.f;
+    o2[1] = (bf16_t)1.f;
+#pragma unroll
+    for (int s = 2; s < 8; ++s) o2[s] = (bf16_t)0.f;
+    bf16_t* dst = X + row * 32;
+    *(bf16x8*)dst = o0;
+    *(bf16x8*)(dst + 8) = o1;
+    *(bf16x8*)(dst + 16) = o2;
+    const bf16x8 z8 = {};
+    *(bf16x8*)(dst + 24) = z8;
+  }
+}
+
+// acc += sign * (cotangent of one slot wrt v = es_recv - es_send), the clip
+// recomputed from the edge states; g is the slot's 12 feature cotangents
+__device__ __forceinline__ void cf_slot_vjp(const float (&er)[12], const float (&se)[12],
+                                            const float (&g)[12], float (&acc)[12],
+                                            float sign, float comm) {
+  const float e0 = er[0] - se[0], e1 = er[1] - se[1], e2 = er[2] - se[2];
+  const float n = sqrtf(1e-6f + e0 * e0 + e1 * e1 + e2 * e2);
+  if (n > comm) {
+    const float inv_n = 1.f / n;
+    const float c3 = (g[0] * e0 + g[1] * e1 + g[2] * e2) * inv_n * inv_n * inv_n;
+    acc[0] += sign * comm * (g[0] * inv_n - e0 * c3);
+    acc[1] += sign * comm * (g[1] * inv_n - e1 * c3);
+    acc[2] += sign * comm * (g[2] * inv_n - e2 * c3);
+  } else {
+    acc[0] += sign * g[0];
+    acc[1] += sign * g[1];
+    acc[2] += sign * g[2];
+  }
+#pragma unroll
+  for (int s = 3; s < 12; ++s) acc[s] += sign * g[s];
+}
+
+// the 12 gradient-carrying columns of one 64 B dX row: two bf16x8 loads
+__device__ __forceinline__ void cf_load_dx(const bf16_t* __restrict__ dx, float (&g)[12]) {
+  const bf16x8 a = *(const bf16x8*)dx, b = *(const bf16x8*)(dx + 8);
+#pragma unroll
+  for (int s = 0; s < 8; ++s) g[s] = (float)a[s];
+#pragma unroll
+  for (int s = 0; s < 4; ++s) g[8 + s] = (float)b[s];
+}
+
+// one thread per node: gather its fixed slot set in a fixed order into d(es),
+// then chain through the transform's jacobian at that node (atomic-free)
+__launch_bounds__(256) __global__
+void edge_msg_in_bwd_cf_kernel(const float* __restrict__ states, const float* __restrict__ es,
+                               const bf16_t* __restrict__ dX, float* __restrict__ dstates,
+                               int B, int N, int R, float comm) {
+  const int D = N + 1 + R;
+  const int V = 2 * N + N * R;
+  const long total = (long)B * V;
+  for (long node = (long)blockIdx.x * blockDim.x + threadIdx.x; node < total;
+       node += (long)gridDim.x * blockDim.x) {
+    const int v = node % V;
+    const long b = node / V;
+    const float* esb = es + b * V * 12;
+    const bf16_t* dxb = dX + b * N * D * 32;
+    float own[12], other[12], g[12], acc[12];
+    cf_load12(esb + (long)v * 12, own);
+#pragma unroll
+    for (int s = 0; s < 12; ++s) acc[s] = 0.f;
+    if (v < N) {
+      // agent j: receiver side over its D slots, sender side in others' rows
+      const int j = v;
+      for (int d = 0; d < D; ++d) {
+        cf_load12(esb + (long)sender_node(j, d, N, R) * 12, other);
+        cf_load_dx(dxb + ((long)j * D + d) * 32, g);
+        cf_slot_vjp(own, other, g, acc, 1.f, comm);
+      }
+      for (int i = 0; i < N; ++i) {
+        cf_load12(esb + (long)i * 12, other);
+        cf_load_dx(dxb + ((long)i * D + j) * 32, g);
+        cf_slot_vjp(other, own, g, acc, -1.f, comm);
+      }
+    } else {
+      // goal j: sender in slot (j, N); lidar hit (j, r): slot (j, N+1+r)
+      const int j = (v < 2 * N) ? v - N : (v - 2 * N) / R;
+      const int d = (v < 2 * N) ? N : N + 1 + (v - 2 * N) % R;
+      cf_load12(esb + (long)j * 12, other);
+      cf_load_dx(dxb + ((long)j * D + d) * 32, g);
+      cf_slot_vjp(other, own, g, acc, -1.f, comm);
+    }
+    float st[12], ds[12];
+    cf_load12(states + node * 12, st);
+    cf_edge_state_vjp(st, acc, ds);
+    cf_store12(dstates + node * 12, ds);
+  }
+}
+
+// fused CrazyFlie.edge_grad_to_state_jac: ge (M,N,D,12) f32 = dh/d(edge
+// feats) -> h_x (M,N,N,12) = dh_i/dx_j. One thread per (m,i,j): the clip vjp
+// of slot (i,j) with the sender sign, for i == j the receiver-side sum over
+// all D slots in slot order, then the transposed transform jacobian of agent j.
+__launch_bounds__(256) __global__
+void crazyflie_edge_jac_kernel(const float* __restrict__ states, const float* __restrict__ es,
+                               const float* __restrict__ ge, float* __restrict__ hx, int M,
+                               int N, int R, float comm) {
+  const int D = N + 1 + R;
+  const int V = 2 * N + N * R;
+  const long total = (long)M * N * N;
+  for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < total;
+       t += (long)gridDim.x * blockDim.x) {
+    const int j = t % N;
+    const int i = (t / N) % N;
+    const long m = t / ((long)N * N);
+    const float* esb = es + m * V * 12;
+    const float* geb = ge + (m * N + i) * D * 12;
+    float er[12], se[12], g[12], acc[12];
+    cf_load12(esb + (long)i * 12, er);
+    cf_load12(esb + (long)j * 12, se);
+    cf_load12(geb + (long)j * 12, g);
+#pragma unroll
+    for (int s = 0; s < 12; ++s) acc[s] = 0.f;
+    cf_slot_vjp(er, se, g, acc, -1.f, comm);
+    if (i == j) {
+      float rs[12];
+#pragma unroll
+      for (int s = 0; s < 12; ++s) rs[s] = 0.f;
+      for (int d = 0; d < D; ++d) {
+        cf_load12(esb + (long)sender_node(i, d, N, R) * 12, se);
+        cf_load12(geb + (long)d * 12, g);
+        cf_slot_vjp(er, se, g, rs, 1.f, comm);
+      }
+#pragma unroll
+      for (int s = 0; s < 12; ++s) acc[s] += rs[s];
+    }
+    float st[12], ds[12];
+    cf_load12(states + (m * V + j) * 12, st);
+    cf_edge_state_vjp(st, acc, ds);
+    cf_store12(hx + t * 12, ds);
   }
 }

@@ -26,11 +26,13 @@ setup(
                 "gcbfplus_amd/ops/hip/optimizer.hip",
                 "gcbfplus_amd/ops/hip/bindings.hip",
             ],
-            # headers: crazyflie_dyn.h is shared by env_step.hip and loss_prep.hip
+            # headers: crazyflie_dyn.h is shared by env_step.hip and loss_prep.hip,
+            # crazyflie_edge.h by the mode-2 and jacobian kernels of edge_msg.hip
             depends=[
                 "gcbfplus_amd/ops/hip/common.h",
                 "gcbfplus_amd/ops/hip/crazyflie_consts.h",
                 "gcbfplus_amd/ops/hip/crazyflie_dyn.h",
+                "gcbfplus_amd/ops/hip/crazyflie_edge.h",
             ],
             extra_compile_args={"cxx": ["-O3"], "nvcc": ["-O3"]},
         )

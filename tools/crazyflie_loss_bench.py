@@ -3,11 +3,14 @@ eager launches (no HIP-graph replay: GCBF_NO_HIPGRAPH=1 is set here), so the
 launch count of the loss prologue shows up in the time.
 
 Two arms are timed in ONE process, alternating round by round: the default
-dispatch, and GCBF_NO_FUSED_PREP=1 (the composed torch prologue). On a commit
-without the fused CrazyFlie prologue the two arms run the same code, and their
-difference is the run-to-run spread. Uses only the public env/algo API and
-``GCBFPlus._loss``, so the same file measures any commit:
-    python tools/crazyflie_loss_bench.py [--label NAME] [--rounds K] [--out FILE]
+dispatch, and an opt-out variable set to 1, chosen with --opt-out:
+GCBF_NO_FUSED_PREP (the composed torch prologue, the default) or
+GCBF_NO_FUSED_EDGE (torch edge_feats instead of the fused layer-0 input). On
+a commit without the fused path in question the two arms run the same code,
+and their difference is the run-to-run spread. Uses only the public env/algo
+API and ``GCBFPlus._loss``, so the same file measures any commit:
+    python tools/crazyflie_loss_bench.py [--label NAME] [--opt-out VAR]
+                                         [--rounds K] [--out FILE]
 Prints one JSON line; kernel launches per minibatch are counted with the
 torch profiler in a separate, untimed pass.
 """
@@ -29,14 +32,16 @@ from gcbfplus_amd.algo import make_algo
 from gcbfplus_amd.env import make_env
 from gcbfplus_amd.trainer.data import FlatBatch
 
-ARMS = ("default", "GCBF_NO_FUSED_PREP=1")
+OPT_OUTS = ("GCBF_NO_FUSED_PREP", "GCBF_NO_FUSED_EDGE")
+ARMS = ("default", "GCBF_NO_FUSED_PREP=1")  # second arm replaced by --opt-out
 
 
 def set_arm(arm):
+    var = ARMS[1].split("=")[0]
     if arm == "default":
-        os.environ.pop("GCBF_NO_FUSED_PREP", None)
+        os.environ.pop(var, None)
     else:
-        os.environ["GCBF_NO_FUSED_PREP"] = "1"
+        os.environ[var] = "1"
 
 
 def minibatch(n, batch, seed):
@@ -87,7 +92,11 @@ def main():
     ap.add_argument("--rounds", type=int, default=15)
     ap.add_argument("--iters", type=int, default=20, help="minibatches per timed sample")
     ap.add_argument("--out", default="")
+    ap.add_argument("--opt-out", default=OPT_OUTS[0], choices=OPT_OUTS,
+                    help="variable the second arm sets to 1")
     args = ap.parse_args()
+    global ARMS
+    ARMS = ("default", args.opt_out + "=1")
     assert torch.cuda.is_available(), "needs a GPU"
     env, algo, mb = minibatch(args.n, args.batch, seed=0)
 
