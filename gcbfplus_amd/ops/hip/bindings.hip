@@ -20,7 +20,7 @@ template <int ACT>
 __global__ void gemm_bias_act_bn128_kernel(const bf16_t_*, const bf16_t_*, const float*, bf16_t_*, int, int, int);
 template <int ACT, bool BT>
 __global__ void gemm_bias_act_glds_kernel(const bf16_t_*, const bf16_t_*, const float*, bf16_t_*, int, int, int);
-__global__ void reduce_dw_db_kernel(const float*, const float*, float*, float*, float*, long, int, int, int);
+__global__ void reduce_dw_db_kernel(const float*, const float*, float*, float*, float*, long, int, int, int, int, int);
 template <int ACT, typename OutT>
 __global__ void gemv_bias_act_kernel(const bf16_t_*, const bf16_t_*, const float*, OutT*, int, int, int);
 template <int ACT>
@@ -388,6 +388,38 @@ torch::Tensor act_bwd(torch::Tensor dy, torch::Tensor y, long act) {
   return dz;
 }
 
+// (S,K,N) + (S,N) partials -> dW, db: dW blocks first (16-byte accesses when
+// K*N, the partial and dW allow), then the scalar db blocks
+static void launch_reduce_dw_db(const float* pw, const float* pb, float* dw, float* db,
+                                float* db2, long K, long N, long S, bool acc,
+                                hipStream_t stream) {
+  const long KN = K * N;
+  const bool vec = (KN & 3) == 0 && ((size_t)pw & 15) == 0 && ((size_t)dw & 15) == 0;
+  const long per = vec ? 256 : 64;
+  const long nbw = (KN + per - 1) / per, nbb = (N + 63) / 64;
+  hipLaunchKernelGGL(reduce_dw_db_kernel, dim3(nbw + nbb), dim3(256), 0, stream, pw, pb, dw,
+                     db, db2, KN, (int)N, (int)S, acc ? 1 : 0, vec ? 1 : 0, (int)nbw);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+}
+
+// the reduction half of gemm_tn on caller-supplied partials
+void reduce_dw_db(torch::Tensor partial, torch::Tensor db_partial, torch::Tensor dw,
+                  torch::Tensor db, c10::optional<torch::Tensor> db2 = c10::nullopt,
+                  bool acc = false) {
+  auto f32 = [](const torch::Tensor& t) {
+    return t.is_cuda() && t.is_contiguous() && t.dtype() == torch::kFloat32;
+  };
+  TORCH_CHECK(f32(partial) && f32(db_partial) && f32(dw) && f32(db));
+  TORCH_CHECK(partial.dim() == 3 && db_partial.dim() == 2);
+  const long S = partial.size(0), K = partial.size(1), N = partial.size(2);
+  TORCH_CHECK(S >= 1 && db_partial.size(0) == S && db_partial.size(1) == N);
+  TORCH_CHECK(dw.numel() == K * N && db.numel() == N);
+  TORCH_CHECK(!db2 || (f32(*db2) && db2->numel() == N));
+  launch_reduce_dw_db(partial.data_ptr<float>(), db_partial.data_ptr<float>(),
+                      dw.data_ptr<float>(), db.data_ptr<float>(),
+                      db2 ? db2->data_ptr<float>() : nullptr, K, N, S, acc, cur_stream());
+}
+
 std::vector<torch::Tensor> gemm_tn_impl(torch::Tensor x, torch::Tensor dz,
                                         torch::Tensor yact, long actin,
                                         torch::Tensor dw, torch::Tensor db, bool acc,
@@ -443,12 +475,9 @@ std::vector<torch::Tensor> gemm_tn_impl(torch::Tensor x, torch::Tensor dz,
     else if (actin == 2) launch(gemm_tn_partial_kernel<2>);
     else launch(gemm_tn_partial_kernel<0>);
   }
-  hipLaunchKernelGGL(reduce_dw_db_kernel, dim3((K * N + N + 255) / 256), dim3(256), 0, stream,
-                     partial.data_ptr<float>(), db_partial.data_ptr<float>(),
-                     dw.data_ptr<float>(), db.data_ptr<float>(),
-                     db2 ? db2->data_ptr<float>() : nullptr, K * N, (int)N, (int)S,
-                     acc ? 1 : 0);
-  C10_HIP_KERNEL_LAUNCH_CHECK();
+  launch_reduce_dw_db(partial.data_ptr<float>(), db_partial.data_ptr<float>(),
+                      dw.data_ptr<float>(), db.data_ptr<float>(),
+                      db2 ? db2->data_ptr<float>() : nullptr, K, N, S, acc, stream);
   return {dw, db};
 }
 
@@ -1142,6 +1171,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("states"), py::arg("action"), py::arg("centers"), py::arg("radii"),
         py::arg("consts"), py::arg("N"), py::arg("R"));
   m.def("crazyflie_step_fits", &crazyflie_step_fits, py::arg("N"), py::arg("K"));
+  m.def("reduce_dw_db", &reduce_dw_db, py::arg("partial"), py::arg("db_partial"),
+        py::arg("dw"), py::arg("db"), py::arg("db2") = py::none(), py::arg("acc") = false);
   m.def("gemm_tn_acc2", &gemm_tn_acc2, py::arg("x"), py::arg("dz"), py::arg("yact"),
         py::arg("actin"), py::arg("dw"), py::arg("db"), py::arg("db2"),
         py::arg("rowgate") = py::none());

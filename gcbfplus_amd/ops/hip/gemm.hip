@@ -596,14 +596,53 @@ template __global__ void gemm_tn_partial_kernel<2>(const bf16_t*, const bf16_t*,
 
 // ---------------------------------------------------------------------------
 // dW computed TRANSPOSED: dW^T[n,k] = sum_m dZ[m,n] X[m,k]. With i=n, j=k,
-// p=m BOTH MFMA operands are m-blocked LDS images ([m/8][col][8]) staged
-// with single b128 vector writes — no scalar transpose stores at all (the
-// 64x64 kernel above spends its time on 8-way scalar LDS writes for the
-// transposed X stage). Global loads are column-wise b16 but lane-coalesced
-// (adjacent lanes take adjacent columns). The 16x16 C fragments are written
-// back transposed so the partial keeps the (S, K, N) layout.
-// Block 64(n) x 64(k), 4 waves 2x2 of 32x32, BMR=64 with register prefetch.
+// p=m both MFMA operands contract over m, the ROW index of both row-major
+// inputs. Both tiles are staged row-major ([m][64 cols], b128 global load ->
+// one b128 LDS store per chunk, like the fwd kernels) and transposed on the
+// read: every operand fragment is two ds_read_b64_tr_b16 (gfx950), each
+// handing a 4(m) x 16(col) block to its 16-lane group column-major. The
+// m -> operand-slot map is the one of the m-blocked images this replaces
+// (lane group g holds rows 32*mm + 8*g + 0..7), so with the same MFMA and the
+// same order over substeps and tiles every slab partial keeps its bits.
+//
+// LDS image: 128-byte rows, 16-byte chunk ch of row m stored at chunk
+// ch ^ tn3_swz(m). Bank check (a/4 mod 64 per 32-lane half for the transposed
+// read, a/4 mod 32 per 8 lanes for the b128 store):
+//   operand read: a half takes rows b+q and b+8+q (q = 0..3) of one 32-byte
+//     column pair. Rows of equal parity share a 128-byte bank half; their
+//     (bit 1, bit 3) differ, so the XOR puts the four pairs in four distinct
+//     32-byte slots: conflict-free. (Plain rows: rows m and m+2 collide.)
+//   db read: a half takes rows b+q of two column pairs that differ in chunk
+//     bit 1, which the XOR of rows q and q+2 swaps: 2-way, 4 reads per tile in
+//     the kb == 0 blocks only.
+//   store: 8 lanes write the 8 chunks of one row, permuted: conflict-free.
+// The transposed read needs EXEC all ones and 8-byte-aligned addresses: no
+// lane-dependent branch surrounds one, trip counts are block-uniform, and
+// ragged tiles are zero-filled, never masked.
+// One tile buffer, two barriers per tile, the next tile's global loads in
+// flight under the MFMAs: a second buffer (one barrier per tile) measured no
+// faster. Block 64(n) x 64(k), 4 waves 2x2 of 32x32, BMR=64.
 // ---------------------------------------------------------------------------
+typedef short tn3_s16x4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) tn3_s16x4 tn3_lds_s16x4;
+
+__device__ __forceinline__ int tn3_swz(int row) { return (row & 2) | ((row >> 1) & 4); }
+
+// element offset of 16-byte chunk ch (0..7) of row `row` in a [64][64] tile
+__device__ __forceinline__ int tn3_off(int row, int ch) {
+  return row * 64 + ((ch ^ tn3_swz(row)) << 3);
+}
+
+// two transposed reads, rows r0..r0+3 and r0+4..r0+7 -> one 8-deep operand;
+// `a` is the lane's address for the block at r0 (4 rows = 256 elements on)
+__device__ __forceinline__ bf16x8 tn3_read_frag(const bf16_t* a) {
+  const tn3_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((tn3_lds_s16x4*)a);
+  const tn3_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((tn3_lds_s16x4*)(a + 4 * 64));
+  typedef short s16x8 __attribute__((ext_vector_type(8)));
+  const s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+  return __builtin_bit_cast(bf16x8, v);
+}
+
 template <int ACT>
 __launch_bounds__(256) __global__
 void gemm_tn_partial3_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ dZ,
@@ -612,9 +651,11 @@ void gemm_tn_partial3_kernel(const bf16_t* __restrict__ X, const bf16_t* __restr
                              float* __restrict__ partial, float* __restrict__ db_partial,
                              int M, int N, int K, int S, int remap) {
   constexpr int BNR = 64, BKD = 64, BMR = 64;
-  __shared__ bf16_t sZ[BMR / 8][BNR][8];  // dZ image (A-operand)
-  __shared__ bf16_t sX[BMR / 8][BKD][8];  // X image (B-operand)
-  __shared__ float sDb[4][BNR];
+  constexpr int TILE = BMR * 64;  // elements of one row-major tile
+  // one array for all LDS: dZ tile | X tile | db exchange
+  __shared__ __attribute__((aligned(16))) unsigned char smem[2 * TILE * 2 + 4 * BNR * 4];
+  bf16_t* const sZ = (bf16_t*)smem;
+  float* const sDb = (float*)(smem + 2 * TILE * 2);
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int w = tid >> 6;
@@ -649,37 +690,37 @@ void gemm_tn_partial3_kernel(const bf16_t* __restrict__ X, const bf16_t* __restr
   float db_acc = 0.f;
   const int db_c = tid & 63, db_q = tid >> 6;
 
-  // staging, 2 chunks per thread each:
-  //   X: column-wise (col = c & 63, m-block = c >> 6): 8 lane-coalesced b16
-  //      global loads -> ONE b128 LDS store (X has no act fold).
-  //   dZ: row-wise like the fwd kernels (row = c >> 3, 8 cols = (c&7)*8):
-  //      b128 dZ (+ b128 Yact for the act fold) -> 8 scalar LDS stores.
-  //      Column-wise dZ staging would read Yact as 8 extra b16 loads per
-  //      chunk — measured as a net step regression.
+  // b128 loads need 16-B alignment: the row base is aligned only when the
+  // row length is a multiple of 8 and the tensor itself starts aligned
+  const bool xvec = (K & 7) == 0 && ((size_t)X & 15) == 0;
+  const bool zvec = (N & 7) == 0 && ((size_t)dZ & 15) == 0 &&
+                    (ACT == 0 || ((size_t)Yact & 15) == 0);
+
+  // staging, 2 chunks per thread and tile, both tiles row-wise
+  // (row = c >> 3, 8 cols = (c & 7) * 8); act fold and row gate in registers
   bf16_t xv[2][8], zv[2][8];
 
   auto load_tile = [&](long m0) {
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int c = tid + h * 256;
-      const int col = c & 63;
-      const long mr0 = m0 + (c >> 6) * 8;
-      const bool kin = k0 + col < K;
+      const long mr = m0 + (c >> 3);
+      const int cc = (c & 7) * 8;
+      if (mr < me && xvec && k0 + cc + 7 < K) {
+        *(bf16x8*)xv[h] = *(const bf16x8*)(X + mr * K + k0 + cc);
+      } else {
 #pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const long mr = mr0 + i;
-        xv[h][i] = (mr < me && kin) ? X[mr * K + k0 + col] : (bf16_t)0.f;
+        for (int i = 0; i < 8; ++i)
+          xv[h][i] = (mr < me && k0 + cc + i < K) ? X[mr * K + k0 + cc + i] : (bf16_t)0.f;
       }
-      const long zr = m0 + (c >> 3);
-      const int nc = (c & 7) * 8;
-      const bool zgated = rowgate != nullptr && zr < me && !rowgate[zr];
+      const bool zgated = rowgate != nullptr && mr < me && !rowgate[mr];
       if (zgated) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) zv[h][i] = (bf16_t)0.f;
-      } else if (zr < me && n0 + nc + 7 < N && (N & 7) == 0) {
-        *(bf16x8*)zv[h] = *(const bf16x8*)(dZ + zr * N + n0 + nc);
+      } else if (mr < me && zvec && n0 + cc + 7 < N) {
+        *(bf16x8*)zv[h] = *(const bf16x8*)(dZ + mr * N + n0 + cc);
         if constexpr (ACT != 0) {
-          bf16x8 yv = *(const bf16x8*)(Yact + zr * N + n0 + nc);
+          bf16x8 yv = *(const bf16x8*)(Yact + mr * N + n0 + cc);
 #pragma unroll
           for (int i = 0; i < 8; ++i)
             zv[h][i] = (bf16_t)((float)zv[h][i] * act_grad_from_out((float)yv[i], ACT));
@@ -687,10 +728,10 @@ void gemm_tn_partial3_kernel(const bf16_t* __restrict__ X, const bf16_t* __restr
       } else {
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-          const bool ok = zr < me && n0 + nc + i < N;
-          float z = ok ? (float)dZ[zr * N + n0 + nc + i] : 0.f;
+          const bool ok = mr < me && n0 + cc + i < N;
+          float z = ok ? (float)dZ[mr * N + n0 + cc + i] : 0.f;
           if constexpr (ACT != 0)
-            if (ok) z *= act_grad_from_out((float)Yact[zr * N + n0 + nc + i], ACT);
+            if (ok) z *= act_grad_from_out((float)Yact[mr * N + n0 + cc + i], ACT);
           zv[h][i] = (bf16_t)z;
         }
       }
@@ -701,15 +742,26 @@ void gemm_tn_partial3_kernel(const bf16_t* __restrict__ X, const bf16_t* __restr
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int c = tid + h * 256;
-      const int col = c & 63;
-      const int mb = c >> 6;
-      *(bf16x8*)(&sX[mb][col][0]) = *(bf16x8*)xv[h];
-      const int zr = c >> 3;
-      const int nc = (c & 7) * 8;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) sZ[zr >> 3][nc + i][zr & 7] = zv[h][i];
+      const int o = tn3_off(c >> 3, c & 7);
+      *(bf16x8*)(sZ + o) = *(bf16x8*)zv[h];
+      *(bf16x8*)(sZ + TILE + o) = *(bf16x8*)xv[h];
     }
   };
+
+  // per-lane addresses of the transposed reads: lane 4q+p of a 16-lane group
+  // points at row q, columns 4p..4p+3 of its block. tn3_swz of an operand
+  // row 32*mm + 8*g + 4*r + q does not depend on mm or r, so those are
+  // constant offsets from one address per fragment.
+  const int g = lane >> 4, tq = (lane >> 2) & 3, tp = lane & 3;
+  int aoff[2], boff[2], doff[4];
+#pragma unroll
+  for (int f = 0; f < 2; ++f) {
+    aoff[f] = tn3_off(8 * g + tq, wi * 4 + f * 2 + (tp >> 1)) + 4 * (tp & 1);
+    boff[f] = TILE + tn3_off(8 * g + tq, wj * 4 + f * 2 + (tp >> 1)) + 4 * (tp & 1);
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+    doff[r] = tn3_off(16 * db_q + 4 * r + tq, g * 2 + (tp >> 1)) + 4 * (tp & 1);
 
   load_tile(ms);
   for (long m0 = ms; m0 < me; m0 += BMR) {
@@ -719,22 +771,23 @@ void gemm_tn_partial3_kernel(const bf16_t* __restrict__ X, const bf16_t* __restr
     if (m0 + BMR < me) load_tile(m0 + BMR);  // overlap with the MFMA below
 
     if (kb == 0) {
+      // column db_c, rows 16*db_q + 0..15 in increasing order
 #pragma unroll
-      for (int q = 0; q < 2; ++q) {
-        const bf16x8 v = *(const bf16x8*)(&sZ[db_q * 2 + q][db_c][0]);
+      for (int r = 0; r < 4; ++r) {
+        const tn3_s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((tn3_lds_s16x4*)(sZ + doff[r]));
+        typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+        const bf16x4 bv = __builtin_bit_cast(bf16x4, v);
 #pragma unroll
-        for (int i = 0; i < 8; ++i) db_acc += (float)v[i];
+        for (int i = 0; i < 4; ++i) db_acc += (float)bv[i];
       }
     }
 #pragma unroll
     for (int mm = 0; mm < 2; ++mm) {  // two 32-deep reduction substeps
       bf16x8 afr[2], bfr[2];
 #pragma unroll
-      for (int nf = 0; nf < 2; ++nf)
-        afr[nf] = *(const bf16x8*)(&sZ[mm * 4 + (lane >> 4)][wi * 32 + nf * 16 + (lane & 15)][0]);
+      for (int nf = 0; nf < 2; ++nf) afr[nf] = tn3_read_frag(sZ + aoff[nf] + mm * 32 * 64);
 #pragma unroll
-      for (int kf = 0; kf < 2; ++kf)
-        bfr[kf] = *(const bf16x8*)(&sX[mm * 4 + (lane >> 4)][wj * 32 + kf * 16 + (lane & 15)][0]);
+      for (int kf = 0; kf < 2; ++kf) bfr[kf] = tn3_read_frag(sZ + boff[kf] + mm * 32 * 64);
 #pragma unroll
       for (int nf = 0; nf < 2; ++nf)
 #pragma unroll
@@ -744,11 +797,11 @@ void gemm_tn_partial3_kernel(const bf16_t* __restrict__ X, const bf16_t* __restr
   }
 
   if (kb == 0) {
-    sDb[db_q][db_c] = db_acc;
+    sDb[db_q * BNR + db_c] = db_acc;
     __syncthreads();
     if (db_q == 0 && n0 + db_c < N)
       db_partial[(long)s * N + n0 + db_c] =
-          (sDb[0][db_c] + sDb[1][db_c]) + (sDb[2][db_c] + sDb[3][db_c]);
+          (sDb[db_c] + sDb[BNR + db_c]) + (sDb[2 * BNR + db_c] + sDb[3 * BNR + db_c]);
   }
 
   // C frag: lane holds C[row = n-frag][col = k-frag]; write transposed into
@@ -1077,30 +1130,56 @@ template __global__ void gemm_tn_partial2_kernel<0>(const bf16_t*, const bf16_t*
 template __global__ void gemm_tn_partial2_kernel<1>(const bf16_t*, const bf16_t*, const bf16_t*, float*, float*, int, int, int, int, int);
 template __global__ void gemm_tn_partial2_kernel<2>(const bf16_t*, const bf16_t*, const bf16_t*, float*, float*, int, int, int, int, int);
 
-// (dw_partial (S,K,N), db_partial (S,N)) -> (dW, db) in ONE launch
-// (fixed-order sums: deterministic; 4 accumulators hide add latency).
+// (dw_partial (S,K,N), db_partial (S,N)) -> (dW, db) in ONE launch.
+// Fixed summation order per output (deterministic):
+//   a_j = sum of src[s], s = j (mod 4), s < 4*(S/4), increasing s;
+//   the remaining s are added to a_0 in order; r = (a0 + a1) + (a2 + a3).
+// The four chains of an output run in parallel, one wave of the block per
+// chain (j = tid >> 6), so a thread's S/4 loads are independent and stay in
+// flight together; chains 1..3 hand their sums to wave 0 through LDS. With
+// vec != 0 a thread of a dW block takes four consecutive outputs as 16-byte
+// loads and stores (launcher: K*N % 4 == 0 and both pointers 16-B aligned).
+// Blocks [0, nbw) cover dW, 64 * (vec ? 4 : 1) outputs each; the rest cover
+// db, 64 outputs each, always scalar.
 // acc != 0 accumulates (+=) into dW/db — used to write straight into the
 // optimizer's flat-gradient views, skipping autograd's AccumulateGrad adds.
-__global__ void reduce_dw_db_kernel(const float* __restrict__ pw, const float* __restrict__ pb,
-                                    float* __restrict__ dW, float* __restrict__ db,
-                                    float* __restrict__ db2,
-                                    long KN, int N, int S, int acc) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const bool is_db = i >= KN;
-  if (i >= KN + N) return;
+__launch_bounds__(256) __global__
+void reduce_dw_db_kernel(const float* __restrict__ pw, const float* __restrict__ pb,
+                         float* __restrict__ dW, float* __restrict__ db,
+                         float* __restrict__ db2,
+                         long KN, int N, int S, int acc, int vec, int nbw) {
+  __shared__ f32x4 sA[3][64];
+  const int lane = threadIdx.x & 63, j = threadIdx.x >> 6;
+  const bool is_db = (int)blockIdx.x >= nbw;  // block-uniform
+  const bool v4 = !is_db && vec;
   const float* src = is_db ? pb : pw;
   const long stride = is_db ? N : KN;
-  const long off = is_db ? i - KN : i;
-  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-  int s = 0;
-  for (; s + 4 <= S; s += 4) {
-    a0 += src[(long)s * stride + off];
-    a1 += src[(long)(s + 1) * stride + off];
-    a2 += src[(long)(s + 2) * stride + off];
-    a3 += src[(long)(s + 3) * stride + off];
+  const long blk = is_db ? (long)blockIdx.x - nbw : (long)blockIdx.x;
+  const long off = (blk * 64 + lane) * (v4 ? 4 : 1);
+  const bool live = off < stride;
+  const int S4 = S & ~3;
+  f32x4 a = {0.f, 0.f, 0.f, 0.f};
+  if (live) {
+    if (v4) {
+#pragma unroll 8
+      for (int s = j; s < S4; s += 4) a += *(const f32x4*)(src + (long)s * stride + off);
+    } else {
+#pragma unroll 8
+      for (int s = j; s < S4; s += 4) a[0] += src[(long)s * stride + off];
+    }
   }
-  for (; s < S; ++s) a0 += src[(long)s * stride + off];
-  const float r = (a0 + a1) + (a2 + a3);
+  if (j != 0) sA[j - 1][lane] = a;
+  __syncthreads();
+  if (j != 0 || !live) return;
+  if (v4) {
+    for (int s = S4; s < S; ++s) a += *(const f32x4*)(src + (long)s * stride + off);
+    const f32x4 r = (a + sA[0][lane]) + (sA[1][lane] + sA[2][lane]);
+    f32x4* dst = (f32x4*)(dW + off);
+    *dst = acc ? (*dst + r) : r;
+    return;
+  }
+  for (int s = S4; s < S; ++s) a[0] += src[(long)s * stride + off];
+  const float r = (a[0] + sA[0][lane][0]) + (sA[1][lane][0] + sA[2][lane][0]);
   float* dst = is_db ? db + off : dW + off;
   *dst = acc ? (*dst + r) : r;
   // optional second db accumulation target (one-hot bias fold: the same db

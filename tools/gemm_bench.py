@@ -22,21 +22,68 @@ def bench(M, K, N, iters=50):
     err = (y[:256].float() - ref).abs().max().item()
     print(f"M={M:6d} K={K:3d} N={N:3d}: {dt*1e6:7.1f} us  {tf:6.1f} TF  maxerr {err:.3f}")
 
-def bench_tn(M, K, N, iters=50):
-    x = torch.randn(M, K, device="cuda").to(torch.bfloat16)
-    dz = torch.randn(M, N, device="cuda").to(torch.bfloat16)
+def _event_us(fn, iters):
+    """Median device time of fn() in microseconds (one event pair per call)."""
     for _ in range(5):
-        dw, db = _C.gemm_tn(x, dz, dz, 0)
+        fn()
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+          for _ in range(iters)]
+    for a, b in ev:
+        a.record()
+        fn()
+        b.record()
     torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(iters):
-        dw, db = _C.gemm_tn(x, dz, dz, 0)
-    torch.cuda.synchronize()
-    dt = (time.perf_counter() - t0) / iters
-    tf = 2 * M * K * N / dt / 1e12
-    ref = x[:, :].float().t() @ dz.float()
-    err = (dw - ref).abs().max().item() / max(1.0, ref.abs().max().item())
-    print(f"TN M={M:6d} K={K:3d} N={N:3d}: {dt*1e6:7.1f} us  {tf:6.1f} TF  relerr {err:.3f}")
+    t = sorted(a.elapsed_time(b) for a, b in ev)
+    return t[len(t) // 2] * 1e3
+
+
+def _tn_split(M, K, N):
+    """Slab count of the dW launcher for the 64x64 kernels (tests/test_gemm_oracle.py)."""
+    gk, gn = (K + 63) // 64, (N + 63) // 64
+    S = min(128, max(1, 1024 // (gk * gn)))
+    S = min(S, max(1, (M + 127) // 128))
+    return (S + 7) // 8 * 8 if S >= 8 else S
+
+
+# dW shapes of one GNNLayer (nn/gnn.py) at M = batch * agents * edge slots, with
+# the activation fold of the layer that owns the weight:
+#   msg_mlp 32->256 relu, 256->256 linear; msg_out 256->128 linear;
+#   attn_mlp 128->128 relu, 128->128 linear; attn_out 128->1 linear
+TN_SHAPES = [(32, 256, 1), (256, 256, 0), (256, 128, 0), (128, 128, 1), (128, 128, 0),
+             (128, 1, 0)]
+
+
+def bench_tn(M, K, N, actin, gated, iters=30):
+    x = torch.randn(M, K, device="cuda").to(torch.bfloat16)
+    dy = torch.randn(M, N, device="cuda").to(torch.bfloat16)
+    y = torch.randn(M, N, device="cuda").relu().to(torch.bfloat16)
+    gate = (torch.rand(M, device="cuda") < 0.5) if gated else None
+    dw = torch.zeros(K, N, device="cuda")
+    db = torch.zeros(N, device="cuda")
+    us = _event_us(lambda: _C.gemm_tn_acc(x, dy, y if actin else dy, actin, dw, db, gate), iters)
+    line = (f"TN M={M:6d} K={K:3d} N={N:3d} actin={actin} gate={'half' if gated else 'none'}: "
+            f"{us:7.1f} us  {2 * M * K * N / us / 1e6:6.1f} TF")
+    if hasattr(_C, "reduce_dw_db"):
+        S = _tn_split(M, K, N)
+        pw = torch.randn(S, K, N, device="cuda")
+        pb = torch.randn(S, N, device="cuda")
+        rus = _event_us(lambda: _C.reduce_dw_db(pw, pb, dw, db, None, True), iters)
+        line += f"  | reduce S={S:3d}: {rus:6.1f} us  {S * K * N * 4 / rus / 1e6:5.2f} TB/s"
+    dz = dy.float() * (y > 0).float() if actin else dy.float()
+    if gated:
+        dz = dz * gate[:, None].float()
+    dw1, _ = _C.gemm_tn(x, dy, y if actin else dy, actin, gate)
+    ref = x.float().t() @ dz.bfloat16().float()
+    err = (dw1 - ref).abs().max().item() / max(1.0, ref.abs().max().item())
+    print(line + f"  relerr {err:.1e}")
+    # the forward glds kernel on the same (M, K, N): the yardstick for a
+    # row-major-staged MFMA loop at this K
+    if N > 16 and not gated:
+        w = torch.randn(K, N, device="cuda").to(torch.bfloat16)
+        b = torch.randn(N, device="cuda")
+        fus = _event_us(lambda: _C.gemm_bias_act(x, w, b, 1), iters)
+        print(f"   fwd {_C.gemm_path('fwd', M, K, N):5s} same shape: {fus:7.1f} us  "
+              f"{2 * M * K * N / fus / 1e6:6.1f} TF")
 
 def bench_gemv(M, K, N, iters=50):
     x = torch.randn(M, K, device="cuda").to(torch.bfloat16)
@@ -59,7 +106,8 @@ if __name__ == "__main__":
     for shape in [(167936, 256, 256), (167936, 32, 256), (167936, 256, 128),
                   (167936, 128, 128), (4096, 256, 256), (4096, 128, 256)]:
         bench(*shape)
-    for shape in [(167936, 256, 256), (167936, 128, 128), (167936, 32, 256), (4096, 256, 256)]:
-        bench_tn(*shape)
+    for K, N, actin in TN_SHAPES:
+        for gated in (False, True):
+            bench_tn(167936, K, N, actin, gated)
     for shape in [(167936, 128, 1), (335872, 128, 1), (4096, 256, 2), (4096, 256, 1)]:
         bench_gemv(*shape)
