@@ -16,10 +16,8 @@ template <int ACT, bool BT, int ACTIN>
 __global__ void gemm_bias_act_kernel(const bf16_t_*, const bf16_t_*, const float*, bf16_t_*, const bf16_t_*, int, int, int);
 template <int ACT, bool BT, int ACTIN>
 __global__ void gemm_bias_act_sm_kernel(const bf16_t_*, const bf16_t_*, const float*, bf16_t_*, const bf16_t_*, int, int, int);
-template <int ACT>
-__global__ void gemm_bias_act_bn128_kernel(const bf16_t_*, const bf16_t_*, const float*, bf16_t_*, int, int, int);
-template <int ACT, bool BT>
-__global__ void gemm_bias_act_glds_kernel(const bf16_t_*, const bf16_t_*, const float*, bf16_t_*, int, int, int);
+template <int ACT, bool BT, int NCH>
+__global__ void gemm_bias_act_panel_kernel(const bf16_t_*, const bf16_t_*, const float*, bf16_t_*, int, int, int, int);
 __global__ void reduce_dw_db_kernel(const float*, const float*, float*, float*, float*, long, int, int, int, int, int);
 template <int ACT, typename OutT>
 __global__ void gemv_bias_act_kernel(const bf16_t_*, const bf16_t_*, const float*, OutT*, int, int, int);
@@ -106,7 +104,7 @@ static inline bf16_t_* bfp_mut(torch::Tensor& t) {
 // ---------------------------------------------------------------------------
 enum GemmOp { GEMM_FWD = 0, GEMM_BT = 1, GEMM_TN = 2 };
 enum GemmKernel {
-  GK_DOT, GK_GEMV, GK_SM, GK_BN128, GK_GLDS, GK_BASE,  // Y = act(X W + b) / dX = dZ W^T
+  GK_DOT, GK_GEMV, GK_SM, GK_GLDS, GK_BASE,  // Y = act(X W + b) / dX = dZ W^T
   GK_TN1, GK_TN2, GK_TN3, GK_TN4                       // dW = X^T dZ partial variants
 };
 
@@ -116,6 +114,7 @@ struct GemmPlan {
   size_t lds;  // dynamic LDS request in bytes (0: static only)
   long gk, gn, S;  // dW: output tile grid and split-M slab count
   bool remap;      // dW: XCD-aware 1-D launch decode
+  int wbufs;       // row-panel kernel: W tile buffers in LDS (2, or 1 when 2 do not fit)
 };
 
 // Dynamic LDS a workgroup may request on the current device, as the runtime
@@ -140,7 +139,7 @@ static size_t gemm_lds_limit() {
 }
 
 static GemmPlan gemm_plan(GemmOp op, long M, long K, long N, long actin, bool gated) {
-  GemmPlan p{GK_BASE, K, 0, 0, 0, 0, false};
+  GemmPlan p{GK_BASE, K, 0, 0, 0, 0, false, 0};
   if (op == GEMM_TN) {
     // kernel variants: 1 = 64x64 transposed-X stage (scalar LDS writes),
     // 2 = 128x128 tile (slower: same scalar staging), 3 = dW^T orientation
@@ -171,7 +170,13 @@ static GemmPlan gemm_plan(GemmOp op, long M, long K, long N, long actin, bool ga
     return p;
   }
   const size_t b_image = (size_t)(K / 8) * 64 * 8 * sizeof(uint16_t);  // [K/8][64][8]
-  const bool glds_ok = M % 128 == 0 && K % 64 == 0 && getenv("GCBF_GEMM_NOGLDS") == nullptr;
+  // row-panel kernel: [128][K] X panel, one or two [64][K] W tiles and the
+  // bias (padded to whole 64-column tiles) in LDS; K/64 <= 6 instantiated
+  const size_t panel = (size_t)128 * K * sizeof(uint16_t) + (size_t)((N + 63) / 64) * 64 * sizeof(float);
+  const size_t wtile = (size_t)64 * K * sizeof(uint16_t);
+  const int wbufs = panel + 2 * wtile <= gemm_lds_limit() ? 2 : 1;
+  const bool glds_ok = M % 128 == 0 && K % 64 == 0 && getenv("GCBF_GEMM_NOGLDS") == nullptr &&
+                       K <= 384 && panel + wbufs * wtile <= gemm_lds_limit();
   if (op == GEMM_FWD) {
     if (N == 1) {  // thread-per-row dot: gate / CBF head
       p.kernel = GK_DOT;
@@ -191,14 +196,11 @@ static GemmPlan gemm_plan(GemmOp op, long M, long K, long N, long actin, bool ga
       // small-M tile: 32x64 so mid-size layers still fill 256 CUs
       p.kernel = GK_SM;
       p.lds = b_image + 32 * 40 * sizeof(uint16_t);
-    } else if (N >= 128 && (N % 128) == 0 && getenv("GCBF_GEMM_BN128") != nullptr) {
-      // BN=128: halves A re-reads for the 256-wide layers
-      p.kernel = GK_BN128;
-      p.lds = 2 * b_image + 128 * 40 * sizeof(uint16_t);
     } else if (glds_ok) {
-      // glds-pipelined path (double-buffered direct-to-LDS A staging)
+      // row-panel path: X read once, everything staged direct-to-LDS
       p.kernel = GK_GLDS;
-      p.lds = b_image + 2 * 128 * 64 * sizeof(uint16_t);
+      p.wbufs = wbufs;
+      p.lds = panel + wbufs * wtile;
     } else {
       p.kernel = GK_BASE;
       p.lds = b_image + 128 * 40 * sizeof(uint16_t);
@@ -211,7 +213,8 @@ static GemmPlan gemm_plan(GemmOp op, long M, long K, long N, long actin, bool ga
     p.lds = b_image + 32 * 40 * sizeof(uint16_t);
   } else if (actin == 0 && glds_ok) {
     p.kernel = GK_GLDS;
-    p.lds = b_image + 2 * 128 * 64 * sizeof(uint16_t);
+    p.wbufs = wbufs;
+    p.lds = panel + wbufs * wtile;
   } else {
     p.kernel = GK_BASE;
     p.lds = b_image + 128 * 40 * sizeof(uint16_t);
@@ -224,7 +227,6 @@ static const char* gemm_kernel_name(GemmKernel k) {
     case GK_DOT: return "dot";
     case GK_GEMV: return "gemv";
     case GK_SM: return "sm";
-    case GK_BN128: return "bn128";
     case GK_GLDS: return "glds";
     case GK_BASE: return "base";
     case GK_TN1: return "tn1";
@@ -245,7 +247,7 @@ static void check_lds(const char* what, const GemmPlan& p, long M, long K, long 
 
 // Launch-free dispatch query: which kernel `op` ("fwd" gemm_bias_act, "bt"
 // gemm_bt, "tn" gemm_tn/_acc/_acc2) runs for this shape under the current
-// env toggles. fwd: "dot" | "gemv" | "sm" | "glds" | "base" | "bn128",
+// env toggles. fwd: "dot" | "gemv" | "sm" | "glds" | "base",
 // prefixed "pad->" when K is zero-padded to %32 first; bt: the same names
 // with a "_bt" suffix; tn: "tn<variant> S=<slabs> remap=<0|1>".
 std::string gemm_path(const std::string& op, long M, long K, long N, long actin, bool gated) {
@@ -273,6 +275,44 @@ std::vector<std::string> gemm_default_paths() {
 }
 
 long gemm_lds_limit_bytes() { return (long)gemm_lds_limit(); }
+
+// Row-panel kernel launch ("glds" / "glds_bt"). Its LDS request exceeds
+// 64 KiB from K = 192 on, so each instantiation raises its dynamic-LDS
+// ceiling once per device: a function attribute, not a stream operation, so
+// the launcher stays legal inside a stream capture.
+template <int ACT, bool BT, int NCH>
+static void launch_panel_nch(const GemmPlan& plan, hipStream_t stream, const bf16_t_* x,
+                             const bf16_t_* w, const float* bias, bf16_t_* y, long M, long N,
+                             bool wvec) {
+  static bool opted[64] = {false};  // per device ordinal
+  int dev = 0;
+  C10_HIP_CHECK(hipGetDevice(&dev));
+  const bool slot = dev >= 0 && dev < 64;
+  if (!slot || !opted[dev]) {
+    C10_HIP_CHECK(hipFuncSetAttribute((const void*)gemm_bias_act_panel_kernel<ACT, BT, NCH>,
+                                      hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)gemm_lds_limit()));
+    if (slot) opted[dev] = true;
+  }
+  hipLaunchKernelGGL((gemm_bias_act_panel_kernel<ACT, BT, NCH>), dim3(M / 128), dim3(256),
+                     plan.lds, stream, x, w, bias, y, (int)M, (int)N, plan.wbufs, (int)wvec);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+}
+
+template <int ACT, bool BT>
+static void launch_panel(const GemmPlan& plan, hipStream_t stream, const bf16_t_* x,
+                         const bf16_t_* w, const float* bias, bf16_t_* y, long M, long N, long K,
+                         bool wvec) {
+  switch (K / 64) {
+    case 1: return launch_panel_nch<ACT, BT, 1>(plan, stream, x, w, bias, y, M, N, wvec);
+    case 2: return launch_panel_nch<ACT, BT, 2>(plan, stream, x, w, bias, y, M, N, wvec);
+    case 3: return launch_panel_nch<ACT, BT, 3>(plan, stream, x, w, bias, y, M, N, wvec);
+    case 4: return launch_panel_nch<ACT, BT, 4>(plan, stream, x, w, bias, y, M, N, wvec);
+    case 5: return launch_panel_nch<ACT, BT, 5>(plan, stream, x, w, bias, y, M, N, wvec);
+    case 6: return launch_panel_nch<ACT, BT, 6>(plan, stream, x, w, bias, y, M, N, wvec);
+  }
+  TORCH_CHECK(false, "row-panel GEMM: no instantiation for K=", K);
+}
 
 torch::Tensor gemm_bias_act(torch::Tensor x, torch::Tensor w, torch::Tensor bias, long act) {
   CHECK_IN(x);
@@ -340,26 +380,12 @@ torch::Tensor gemm_bias_act(torch::Tensor x, torch::Tensor w, torch::Tensor bias
     if (act == 0) launch(gemm_bias_act_sm_kernel<0, false, 0>);
     else if (act == 1) launch(gemm_bias_act_sm_kernel<1, false, 0>);
     else launch(gemm_bias_act_sm_kernel<2, false, 0>);
-  } else if (plan.kernel == GK_BN128) {
-    dim3 grid((M + 127) / 128, N / 128);
-    auto launch = [&](auto kernel) {
-      hipLaunchKernelGGL(kernel, grid, dim3(256), smem, stream, bfp(x), bfp(w),
-                         bias.data_ptr<float>(), bfp_mut(y), (int)M, (int)N, (int)K);
-      C10_HIP_KERNEL_LAUNCH_CHECK();
-    };
-    if (act == 0) launch(gemm_bias_act_bn128_kernel<0>);
-    else if (act == 1) launch(gemm_bias_act_bn128_kernel<1>);
-    else launch(gemm_bias_act_bn128_kernel<2>);
   } else if (plan.kernel == GK_GLDS) {
-    dim3 grid(M / 128, (N + 63) / 64);
-    auto launch = [&](auto kernel) {
-      hipLaunchKernelGGL(kernel, grid, dim3(256), smem, stream, bfp(x), bfp(w),
-                         bias.data_ptr<float>(), bfp_mut(y), (int)M, (int)N, (int)K);
-      C10_HIP_KERNEL_LAUNCH_CHECK();
-    };
-    if (act == 0) launch(gemm_bias_act_glds_kernel<0, false>);
-    else if (act == 1) launch(gemm_bias_act_glds_kernel<1, false>);
-    else launch(gemm_bias_act_glds_kernel<2, false>);
+    // DMA of a W tile needs 16-byte-aligned rows: N % 8 == 0 and an aligned W
+    const bool wvec = N % 8 == 0 && ((uintptr_t)w.data_ptr() & 15) == 0;
+    if (act == 0) launch_panel<0, false>(plan, stream, bfp(x), bfp(w), bias.data_ptr<float>(), bfp_mut(y), M, N, K, wvec);
+    else if (act == 1) launch_panel<1, false>(plan, stream, bfp(x), bfp(w), bias.data_ptr<float>(), bfp_mut(y), M, N, K, wvec);
+    else launch_panel<2, false>(plan, stream, bfp(x), bfp(w), bias.data_ptr<float>(), bfp_mut(y), M, N, K, wvec);
   } else {
     dim3 grid((M + 127) / 128, (N + 63) / 64);
     auto launch = [&](auto kernel) {
@@ -542,10 +568,8 @@ torch::Tensor gemm_bt(torch::Tensor dz, torch::Tensor w, torch::Tensor yact, lon
     else if (actin == 2) launch(gemm_bias_act_sm_kernel<0, true, 2>);
     else launch(gemm_bias_act_sm_kernel<0, true, 0>);
   } else if (plan.kernel == GK_GLDS) {
-    dim3 grid(M / 128, (N + 63) / 64);
-    hipLaunchKernelGGL((gemm_bias_act_glds_kernel<0, true>), grid, dim3(256), smem, stream,
-                       bfp(dz), bfp(w), bias, bfp_mut(y), (int)M, (int)N, (int)K);
-    C10_HIP_KERNEL_LAUNCH_CHECK();
+    const bool wvec = ((uintptr_t)w.data_ptr() & 15) == 0;  // rows: K % 64 == 0
+    launch_panel<0, true>(plan, stream, bfp(dz), bfp(w), bias, bfp_mut(y), M, N, K, wvec);
   } else {
     dim3 grid((M + 127) / 128, (N + 63) / 64);
     auto launch = [&](auto kernel) {

@@ -10,10 +10,11 @@
 //                               transposed B-stage (backward dX without a
 //                               transpose copy); ACTIN folds the upstream
 //                               activation backward into the A-stage.
-//   gemm_bias_act_glds_kernel : BK=64 double-buffered direct-to-LDS A staging
-//                               (global_load_lds) for M%128==0, K%64==0.
+//   gemm_bias_act_panel_kernel: row panel for M%128==0, K%64==0, K<=384: a
+//                               workgroup keeps 128 rows of X in LDS and
+//                               produces every output column; X, W by
+//                               global_load_lds ("glds" / "glds_bt" paths).
 //   gemm_bias_act_sm_kernel   : 32x64 tile so mid-size M still fills 256 CUs.
-//   gemm_bias_act_bn128_kernel: BN=128 experiment (GCBF_GEMM_BN128 env).
 //   dot_bias_act_kernel       : N == 1 gate/head outputs, thread-per-row.
 //   gemv_bias_act_kernel      : 2 <= N <= 16 outputs, wave-per-row, f32 out.
 //   gemm_tn_partial + reduce  : dW = X^T @ dZ, deterministic split-M partials
@@ -162,100 +163,6 @@ void gemm_bias_act_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict
   }
 }
 
-
-// ---------------------------------------------------------------------------
-// BN=128 variant: halves the A re-read traffic for N=256 layers.
-// grid: (ceil(M/128), ceil(N/128)); 4 waves 2x2, wave tile 64x64.
-// ---------------------------------------------------------------------------
-template <int ACT>
-__launch_bounds__(256) __global__
-void gemm_bias_act_bn128_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ W,
-                                const float* __restrict__ bias, bf16_t* __restrict__ Y,
-                                int M, int N, int K) {
-  constexpr int BM = 128, BN = 128, BK = 32, APAD = 40;
-  extern __shared__ char smem[];
-  bf16_t* sB = (bf16_t*)smem;                                        // [K/8][BN][8]
-  bf16_t* sA = (bf16_t*)(smem + (K / 8) * BN * 8 * sizeof(bf16_t));  // [BM][APAD]
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int w = tid >> 6;
-  const int wm = w >> 1, wn = w & 1;  // wave tile: 64(M) x 64(N)
-  const int m0 = blockIdx.x * BM;
-  const int n0 = blockIdx.y * BN;
-
-  for (int c = tid; c < K * 16; c += 256) {
-    const int k = c >> 4;
-    const int co = (c & 15) * 8;
-    bf16_t v[8];
-    if (n0 + co + 7 < N) {
-      *(bf16x8*)v = *(const bf16x8*)(W + (long)k * N + n0 + co);
-    } else {
-#pragma unroll
-      for (int i = 0; i < 8; ++i)
-        v[i] = (n0 + co + i < N) ? W[(long)k * N + n0 + co + i] : (bf16_t)0.f;
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) sB[((k >> 3) * BN + (co + i)) * 8 + (k & 7)] = v[i];
-  }
-
-  f32x4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  const int arow = tid >> 1;
-  const int acol = (tid & 1) * 16;
-  for (int k0 = 0; k0 < K; k0 += BK) {
-    __syncthreads();
-    bf16_t av[16];
-    const long arow_g = (long)(m0 + arow);
-    if (arow_g < M) {
-      *(bf16x8*)av = *(const bf16x8*)(X + arow_g * K + k0 + acol);
-      *(bf16x8*)(av + 8) = *(const bf16x8*)(X + arow_g * K + k0 + acol + 8);
-    } else {
-#pragma unroll
-      for (int i = 0; i < 16; ++i) av[i] = (bf16_t)0.f;
-    }
-#pragma unroll
-    for (int i = 0; i < 16; i += 8) *(bf16x8*)(sA + arow * APAD + acol + i) = *(bf16x8*)(av + i);
-    __syncthreads();
-
-    bf16x8 afr[4];
-#pragma unroll
-    for (int mf = 0; mf < 4; ++mf)
-      afr[mf] = *(const bf16x8*)(sA + (wm * 64 + mf * 16 + (lane & 15)) * APAD + (lane >> 4) * 8);
-    bf16x8 bfr[4];
-#pragma unroll
-    for (int nf = 0; nf < 4; ++nf)
-      bfr[nf] = *(const bf16x8*)(sB + (((k0 >> 3) + (lane >> 4)) * BN + wn * 64 + nf * 16 + (lane & 15)) * 8);
-#pragma unroll
-    for (int mf = 0; mf < 4; ++mf)
-#pragma unroll
-      for (int nf = 0; nf < 4; ++nf)
-        acc[mf][nf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afr[mf], bfr[nf], acc[mf][nf], 0, 0, 0);
-  }
-
-#pragma unroll
-  for (int mf = 0; mf < 4; ++mf) {
-#pragma unroll
-    for (int nf = 0; nf < 4; ++nf) {
-      const int col = n0 + wn * 64 + nf * 16 + (lane & 15);
-      if (col >= N) continue;
-      const float bv = bias[col];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const long row = m0 + wm * 64 + mf * 16 + (lane >> 4) * 4 + r;
-        if (row < M) Y[row * N + col] = (bf16_t)apply_act(acc[mf][nf][r] + bv, ACT);
-      }
-    }
-  }
-}
-
-template __global__ void gemm_bias_act_bn128_kernel<0>(const bf16_t*, const bf16_t*, const float*, bf16_t*, int, int, int);
-template __global__ void gemm_bias_act_bn128_kernel<1>(const bf16_t*, const bf16_t*, const float*, bf16_t*, int, int, int);
-template __global__ void gemm_bias_act_bn128_kernel<2>(const bf16_t*, const bf16_t*, const float*, bf16_t*, int, int, int);
 
 // ---------------------------------------------------------------------------
 // Small-M variant: BM=32 x BN=64 tile (4 waves as 2x2, wave 16x32) so
@@ -1204,100 +1111,350 @@ template __global__ void gemv_bias_act_kernel<1, float>(const bf16_t*, const bf1
 template __global__ void gemv_bias_act_kernel<2, float>(const bf16_t*, const bf16_t*, const float*, float*, int, int, int);
 
 // ---------------------------------------------------------------------------
-// glds-pipelined main GEMM: BK=64, double-buffered A staged by
-// global_load_lds (16 B per lane), XOR-swizzled LDS image so the b128
-// fragment reads stay bank-conflict-free (granule g' = g ^ ((row>>1)&7) on
-// the [128][64] bf16 tile). Requires M % 128 == 0 and K % 64 == 0 (glds has
-// no per-lane predication); the launcher falls back otherwise.
+// Row-panel GEMM (dispatch names "glds" / "glds_bt"): one workgroup owns 128
+// rows of X and produces EVERY output column for them, so X is read from
+// memory once per call, not once per 64-column tile. Needs M % 128 == 0 and
+// K % 64 == 0 (global_load_lds has no per-lane predicate); grid M/128.
+//
+// LDS, all filled by 16-byte global_load_lds (1 KiB per wave instruction,
+// lane-linear destination, swizzle applied to the per-lane SOURCE address):
+//   panel  [K/64][128][64]  the X slice, staged once; 16-byte granule g of a
+//          row sits at granule g ^ ((row >> 1) & 7), A fragments are b128 reads
+//   W tile (x nbuf, 1 or 2), the slice of W for one 64-column n-tile:
+//     BT   W is (Nout, K) row-major; image [K/64][64 n][64 k], the panel's
+//          swizzle; a B fragment is 8 consecutive k of one row: one b128 read
+//     fwd  W is (K, N) row-major; image [K][64 n] in the row-major layout of
+//          the dW tiles (tn3_off); B fragments by ds_read_b64_tr_b16
+//   bias   [ceil(N/64)*64] f32, zero past N
+//   256*K + nbuf*128*K bytes + bias. With two buffers the DMA of tile t+1 is
+//   issued before the MFMAs of tile t; with one (K = 384) it follows them.
+// A tile whose DMA would touch bytes outside W (last tile of N % 64 != 0) or
+// whose rows are not 16-byte aligned (wvec == 0: forward N % 8 != 0, or an
+// unaligned W) is staged through registers into the same image, predicated
+// and zero-filled.
+// The epilogue of tile t is issued after the DMA of tile t+1 and ahead of the
+// MFMAs of tile t+1 (two-buffer case), so the barrier's wait for that DMA,
+// which also waits for outstanding stores, finds both long done.
+// While a DMA is in flight the compiler puts s_waitcnt vmcnt(0) in front of
+// every LDS read it can see (the DMA may alias it) and of every use of a
+// global load, which would drain the DMA and the stores ahead of the MFMAs.
+// So the fragment reads are inline assembly with their own s_waitcnt lgkmcnt,
+// the k loop is unrolled in full (NCH = K/64 is a template argument: no read
+// is pending over a back edge, where a register copy could be placed), and
+// the bias of a tile is read from LDS before the next DMA is issued. The
+// barrier discipline, not the compiler, orders DMA and fragment reads.
+// MFMA, k -> operand-slot map (lane group lane>>4 holds k = 32*step + 8*group
+// + 0..7, steps ascending) and acc + bias -> act -> bf16 are those of
+// gemm_bias_act_kernel: outputs are bit-identical to it.
+// The transposed reads need EXEC all ones: no lane-dependent branch surrounds
+// the k loop, and ragged tiles are zero-filled, never masked.
 // ---------------------------------------------------------------------------
-template <int ACT, bool BT>
+template <bool BT>
+__device__ __forceinline__ void panel_stage_w(const bf16_t* __restrict__ W, bf16_t* buf,
+                                              int N, int K, int n0, bool dma, bool wvec,
+                                              int tid) {
+  const int lane = tid & 63, w = tid >> 6;
+  if (dma) {
+    if constexpr (BT) {
+      // per 64-wide k chunk: 64 rows x 128 B = 8 wave instructions
+      for (int j = w; j < (K >> 6) * 8; j += 4) {
+        const int c = j >> 3;
+        const int idx = (j & 7) * 64 + lane;
+        const int row = idx >> 3;
+        const int gsrc = (idx & 7) ^ ((row >> 1) & 7);
+        const bf16_t* src = W + (long)(n0 + row) * K + c * 64 + gsrc * 8;
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) uint32_t*)src,
+                                         (__attribute__((address_space(3))) uint32_t*)(buf + (long)j * 512),
+                                         16, 0, 0);
+      }
+    } else {
+      // 8 rows of k x 128 B per wave instruction
+      for (int j = w; j < (K >> 3); j += 4) {
+        const int row = j * 8 + (lane >> 3);
+        const int csrc = (lane & 7) ^ tn3_swz(row);
+        const bf16_t* src = W + (long)row * N + n0 + csrc * 8;
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) uint32_t*)src,
+                                         (__attribute__((address_space(3))) uint32_t*)(buf + (long)j * 512),
+                                         16, 0, 0);
+      }
+    }
+    return;
+  }
+  if constexpr (BT) {
+    const int kch = K >> 3;
+    for (int c = tid; c < 64 * kch; c += 256) {
+      const int r = c / kch;
+      const int kg = c % kch;  // 16-byte granule along K
+      bf16x8 v;
+      if (n0 + r < N) {
+        v = *(const bf16x8*)(W + (long)(n0 + r) * K + kg * 8);
+      } else {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[i] = (bf16_t)0.f;
+      }
+      *(bf16x8*)(buf + (kg >> 3) * 4096 + r * 64 + (((kg & 7) ^ ((r >> 1) & 7)) << 3)) = v;
+    }
+  } else {
+    for (int c = tid; c < K * 8; c += 256) {
+      const int k = c >> 3;
+      const int ch = c & 7;
+      const int co = ch * 8;
+      bf16x8 v;
+      if (wvec && n0 + co + 7 < N) {
+        v = *(const bf16x8*)(W + (long)k * N + n0 + co);
+      } else {
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+          v[i] = (n0 + co + i < N) ? W[(long)k * N + n0 + co + i] : (bf16_t)0.f;
+      }
+      *(bf16x8*)(buf + tn3_off(k, ch)) = v;
+    }
+  }
+}
+
+typedef int panel_i32x4 __attribute__((ext_vector_type(4)));
+typedef int panel_i32x2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ unsigned panel_lds_addr(const void* p) {
+  return (unsigned)(size_t)(const __attribute__((address_space(3))) char*)p;
+}
+
+// fragments of one 32-deep step, as issued (not yet waited for)
+template <bool BT>
+struct PanelFrags {
+  panel_i32x4 a[4];
+  panel_i32x4 b[2];       // BT: one b128 per n fragment
+  panel_i32x2 blo[2], bhi[2];  // fwd: two transposed 64-bit reads per n fragment
+};
+
+// `hold`: the fragments of the step whose MFMAs follow. They pass through the
+// statement so that those MFMAs cannot be scheduled ahead of these reads
+// (which would let one register set serve both steps and serialize them).
+#define PANEL_A_READS(A)                 \
+  "ds_read_b128 %0, %" A "\n\t"            \
+  "ds_read_b128 %1, %" A " offset:2048\n\t" \
+  "ds_read_b128 %2, %" A " offset:4096\n\t" \
+  "ds_read_b128 %3, %" A " offset:6144\n\t"
+template <bool BT>
+__device__ __forceinline__ void panel_issue(PanelFrags<BT>& f, unsigned aaddr, unsigned b0addr,
+                                            unsigned b1addr, PanelFrags<BT>* hold) {
+  if constexpr (BT) {
+    if (hold != nullptr) {
+      asm volatile(PANEL_A_READS("12")
+                   "ds_read_b128 %4, %13\n\t"
+                   "ds_read_b128 %5, %14"
+                   : "=&v"(f.a[0]), "=&v"(f.a[1]), "=&v"(f.a[2]), "=&v"(f.a[3]), "=&v"(f.b[0]),
+                     "=&v"(f.b[1]), "+v"(hold->a[0]), "+v"(hold->a[1]), "+v"(hold->a[2]),
+                     "+v"(hold->a[3]), "+v"(hold->b[0]), "+v"(hold->b[1])
+                   : "v"(aaddr), "v"(b0addr), "v"(b1addr));
+    } else {
+      asm volatile(PANEL_A_READS("6")
+                   "ds_read_b128 %4, %7\n\t"
+                   "ds_read_b128 %5, %8"
+                   : "=&v"(f.a[0]), "=&v"(f.a[1]), "=&v"(f.a[2]), "=&v"(f.a[3]), "=&v"(f.b[0]),
+                     "=&v"(f.b[1])
+                   : "v"(aaddr), "v"(b0addr), "v"(b1addr));
+    }
+  } else {
+    if (hold != nullptr) {
+      asm volatile(PANEL_A_READS("14")
+                   "ds_read_b64_tr_b16 %4, %15\n\t"
+                   "ds_read_b64_tr_b16 %5, %15 offset:512\n\t"
+                   "ds_read_b64_tr_b16 %6, %16\n\t"
+                   "ds_read_b64_tr_b16 %7, %16 offset:512"
+                   : "=&v"(f.a[0]), "=&v"(f.a[1]), "=&v"(f.a[2]), "=&v"(f.a[3]), "=&v"(f.blo[0]),
+                     "=&v"(f.bhi[0]), "=&v"(f.blo[1]), "=&v"(f.bhi[1]), "+v"(hold->a[0]),
+                     "+v"(hold->a[1]), "+v"(hold->a[2]), "+v"(hold->a[3]), "+v"(hold->b[0]),
+                     "+v"(hold->b[1])
+                   : "v"(aaddr), "v"(b0addr), "v"(b1addr));
+    } else {
+      asm volatile(PANEL_A_READS("8")
+                   "ds_read_b64_tr_b16 %4, %9\n\t"
+                   "ds_read_b64_tr_b16 %5, %9 offset:512\n\t"
+                   "ds_read_b64_tr_b16 %6, %10\n\t"
+                   "ds_read_b64_tr_b16 %7, %10 offset:512"
+                   : "=&v"(f.a[0]), "=&v"(f.a[1]), "=&v"(f.a[2]), "=&v"(f.a[3]), "=&v"(f.blo[0]),
+                     "=&v"(f.bhi[0]), "=&v"(f.blo[1]), "=&v"(f.bhi[1])
+                   : "v"(aaddr), "v"(b0addr), "v"(b1addr));
+    }
+  }
+}
+#undef PANEL_A_READS
+
+// wait for every issued read; the fragments pass through the statement so no
+// use of them can be scheduled ahead of it
+template <bool BT>
+__device__ __forceinline__ void panel_wait(PanelFrags<BT>& f) {
+  if constexpr (BT) {
+    asm volatile("s_waitcnt lgkmcnt(0)"
+                 : "+v"(f.a[0]), "+v"(f.a[1]), "+v"(f.a[2]), "+v"(f.a[3]), "+v"(f.b[0]),
+                   "+v"(f.b[1]));
+  } else {
+    asm volatile("s_waitcnt lgkmcnt(0)"
+                 : "+v"(f.a[0]), "+v"(f.a[1]), "+v"(f.a[2]), "+v"(f.a[3]), "+v"(f.blo[0]),
+                   "+v"(f.bhi[0]), "+v"(f.blo[1]), "+v"(f.bhi[1]));
+    f.b[0] = panel_i32x4{f.blo[0][0], f.blo[0][1], f.bhi[0][0], f.bhi[0][1]};
+    f.b[1] = panel_i32x4{f.blo[1][0], f.blo[1][1], f.bhi[1][0], f.bhi[1][1]};
+  }
+}
+
+template <int ACT, bool BT, int NCH>
 __launch_bounds__(256) __global__
-void gemm_bias_act_glds_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ W,
-                               const float* __restrict__ bias, bf16_t* __restrict__ Y,
-                               int M, int N, int K) {
-  constexpr int BM = 128, BN = 64, BK = 64;
+void gemm_bias_act_panel_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ W,
+                                const float* __restrict__ bias, bf16_t* __restrict__ Y,
+                                int M, int N, int nbuf, int wvec) {
+  constexpr int BM = 128, BN = 64, K = NCH * 64;
   extern __shared__ char smem[];
-  bf16_t* sB = (bf16_t*)smem;                                    // [K/8][BN][8]
-  bf16_t* sA = (bf16_t*)(smem + (K / 8) * BN * 8 * sizeof(bf16_t));  // [2][128][64]
+  bf16_t* const sA = (bf16_t*)smem;  // [NCH][128][64]
+  bf16_t* const sW = sA + BM * K;    // nbuf x (64 * K)
+  float* const sBias = (float*)(sW + nbuf * (BN * K));
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int w = tid >> 6;
   const int wm = w >> 1, wn = w & 1;  // wave tile: 64(M) x 32(N)
   const int m0 = blockIdx.x * BM;
-  const int n0 = blockIdx.y * BN;
+  const int ntiles = (N + BN - 1) / BN;
 
-  // B preload (same image as the base kernel)
-  stage_B_image<BT>(W, sB, N, K, n0, tid);
+  // ---- bias first: no global load may be waited for under a DMA ----------
+  for (int i = tid; i < ntiles * BN; i += 256) sBias[i] = i < N ? bias[i] : 0.f;
 
-  // glds stage of one A tile into buffer `buf`: 16 wave-chunks of 1 KiB
-  auto stage_A = [&](int k0, int buf) {
-    bf16_t* dstbase = sA + buf * 128 * 64;
+  // ---- the X panel: 16 wave instructions per 64-wide k chunk --------------
 #pragma unroll
-    for (int it = 0; it < 4; ++it) {
-      const int idx = (it * 4 + w) * 64 + lane;  // 16-byte granule index
-      const int row = idx >> 3;
-      const int g = idx & 7;
-      const int gsrc = g ^ ((row >> 1) & 7);     // pre-swizzled source
-      const bf16_t* src = X + (long)(m0 + row) * K + k0 + gsrc * 8;
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) uint32_t*)src,
-                                       (__attribute__((address_space(3))) uint32_t*)(dstbase + (long)(it * 4 + w) * 512),
-                                       16, 0, 0);
+  for (int it = 0; it < NCH * 4; ++it) {
+    const int j = it * 4 + w;
+    const int c = j >> 4;
+    const int idx = (j & 15) * 64 + lane;  // 16-byte granule index in the chunk
+    const int row = idx >> 3;
+    const int gsrc = (idx & 7) ^ ((row >> 1) & 7);
+    const bf16_t* src = X + (long)(m0 + row) * K + c * 64 + gsrc * 8;
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) uint32_t*)src,
+                                     (__attribute__((address_space(3))) uint32_t*)(sA + (long)j * 512),
+                                     16, 0, 0);
+  }
+  auto tile_dma = [&](int t) { return wvec != 0 && (t + 1) * BN <= N; };
+  panel_stage_w<BT>(W, sW, N, K, 0, tile_dma(0), wvec != 0, tid);
+
+  // ---- per-lane fragment addresses (LDS bytes) ----------------------------
+  const int g = lane >> 4;
+  const int sw = (lane >> 1) & 7;  // (row >> 1) & 7 of every fragment row
+  unsigned aaddr[2];               // A fragment mf = 0, k step parity 0/1
+#pragma unroll
+  for (int kk = 0; kk < 2; ++kk)
+    aaddr[kk] = panel_lds_addr(sA) +
+                2 * ((wm * 64 + (lane & 15)) * 64 + (((kk * 4 + g) ^ sw) << 3));
+  unsigned boff[2][2];  // BT: [nf][kk] in a k chunk; fwd: [nf][0] in a 32-deep step
+  if constexpr (BT) {
+#pragma unroll
+    for (int nf = 0; nf < 2; ++nf)
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk)
+        boff[nf][kk] = 2 * ((wn * 32 + nf * 16 + (lane & 15)) * 64 + (((kk * 4 + g) ^ sw) << 3));
+  } else {
+    const int tq = (lane >> 2) & 3, tp = lane & 3;
+#pragma unroll
+    for (int nf = 0; nf < 2; ++nf) {
+      boff[nf][0] = 2 * (tn3_off(8 * g + tq, wn * 4 + nf * 2 + (tp >> 1)) + 4 * (tp & 1));
+      boff[nf][1] = 0;
+    }
+  }
+
+  // issue the fragment reads of 32-deep step s (chunk s >> 1, half s & 1)
+  auto issue = [&](PanelFrags<BT>& f, unsigned wbase, int s, PanelFrags<BT>* hold) {
+    const unsigned a = aaddr[s & 1] + (s >> 1) * (BM * 64 * 2);
+    if constexpr (BT)
+      panel_issue<BT>(f, a, wbase + (s >> 1) * 8192 + boff[0][s & 1],
+                      wbase + (s >> 1) * 8192 + boff[1][s & 1], hold);
+    else
+      panel_issue<BT>(f, a, wbase + s * 4096 + boff[0][0], wbase + s * 4096 + boff[1][0], hold);
+  };
+
+  auto read_bias = [&](float (&bv)[2], int n0) {
+#pragma unroll
+    for (int nf = 0; nf < 2; ++nf) bv[nf] = sBias[n0 + wn * 32 + nf * 16 + (lane & 15)];
+  };
+
+  auto epilogue = [&](const f32x4 (&acc)[4][2], const float (&bv)[2], int n0) {
+#pragma unroll
+    for (int mf = 0; mf < 4; ++mf) {
+#pragma unroll
+      for (int nf = 0; nf < 2; ++nf) {
+        const int col = n0 + wn * 32 + nf * 16 + (lane & 15);
+        if (col >= N) continue;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const long row = m0 + wm * 64 + mf * 16 + (lane >> 4) * 4 + r;
+          Y[row * N + col] = (bf16_t)apply_act(acc[mf][nf][r] + bv[nf], ACT);
+        }
+      }
     }
   };
 
-  f32x4 acc[4][2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  stage_A(0, 0);
-  const int ntiles = K / BK;
+  f32x4 acc[4][2], prev[4][2];
+  float bv[2];
   for (int t = 0; t < ntiles; ++t) {
-    __syncthreads();  // drains the in-flight glds for buffer t&1
-    if (t + 1 < ntiles) stage_A((t + 1) * BK, (t + 1) & 1);
-    const bf16_t* buf = sA + (t & 1) * 128 * 64;
+    __syncthreads();  // W tile t (and at t == 0 the panel and the bias) has landed
+    const bf16_t* wb = sW + ((nbuf == 2) ? (t & 1) : 0) * (BN * K);
+    if (nbuf == 2) {
+      if (t > 0) read_bias(bv, (t - 1) * BN);  // ahead of the DMA
+      if (t + 1 < ntiles)
+        panel_stage_w<BT>(W, sW + ((t + 1) & 1) * (BN * K), N, K, (t + 1) * BN, tile_dma(t + 1),
+                          wvec != 0, tid);
+      if (t > 0) epilogue(prev, bv, (t - 1) * BN);
+    }
+
 #pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {  // two 16x16x32 K-steps per tile
-      bf16x8 afr[4];
+    for (int i = 0; i < 4; ++i)
 #pragma unroll
-      for (int mf = 0; mf < 4; ++mf) {
-        const int row = wm * 64 + mf * 16 + (lane & 15);
-        const int g = kk * 4 + (lane >> 4);
-        const int gs = g ^ ((row >> 1) & 7);
-        afr[mf] = *(const bf16x8*)(buf + (long)row * 64 + gs * 8);
-      }
-      bf16x8 bfr[2];
-      const int kb = t * BK + kk * 32;
+      for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const unsigned wbase = panel_lds_addr(wb);
+    PanelFrags<BT> f[2];
+    issue(f[0], wbase, 0, nullptr);
 #pragma unroll
-      for (int nf = 0; nf < 2; ++nf)
-        bfr[nf] = *(const bf16x8*)(sB + (((kb >> 3) + (lane >> 4)) * BN + wn * 32 + nf * 16 + (lane & 15)) * 8);
+    for (int s = 0; s < 2 * NCH; ++s) {  // reads of step s+1 issue under the MFMAs of step s
+      PanelFrags<BT>& cur = f[s & 1];
+      panel_wait<BT>(cur);
+      if (s + 1 < 2 * NCH) issue(f[(s + 1) & 1], wbase, s + 1, &cur);
 #pragma unroll
       for (int mf = 0; mf < 4; ++mf)
 #pragma unroll
         for (int nf = 0; nf < 2; ++nf)
-          acc[mf][nf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afr[mf], bfr[nf], acc[mf][nf], 0, 0, 0);
+          acc[mf][nf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              __builtin_bit_cast(bf16x8, cur.a[mf]), __builtin_bit_cast(bf16x8, cur.b[nf]),
+              acc[mf][nf], 0, 0, 0);
+      // keep the next step's wait behind these MFMAs
+      __builtin_amdgcn_sched_barrier(0);
+    }
+
+    if (nbuf == 2) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) prev[i][j] = acc[i][j];
+    } else {
+      read_bias(bv, t * BN);
+      if (t + 1 < ntiles) {
+        __syncthreads();  // every wave is done reading the one W buffer
+        panel_stage_w<BT>(W, sW, N, K, (t + 1) * BN, tile_dma(t + 1), wvec != 0, tid);
+      }
+      epilogue(acc, bv, t * BN);  // stores go out while the DMA is in flight
     }
   }
-
-#pragma unroll
-  for (int mf = 0; mf < 4; ++mf) {
-#pragma unroll
-    for (int nf = 0; nf < 2; ++nf) {
-      const int col = n0 + wn * 32 + nf * 16 + (lane & 15);
-      if (col >= N) continue;
-      const float bv = bias[col];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const long row = m0 + wm * 64 + mf * 16 + (lane >> 4) * 4 + r;
-        Y[row * N + col] = (bf16_t)apply_act(acc[mf][nf][r] + bv, ACT);
-      }
-    }
+  if (nbuf == 2) {
+    read_bias(bv, (ntiles - 1) * BN);
+    epilogue(prev, bv, (ntiles - 1) * BN);
   }
 }
 
-template __global__ void gemm_bias_act_glds_kernel<0, false>(const bf16_t*, const bf16_t*, const float*, bf16_t*, int, int, int);
-template __global__ void gemm_bias_act_glds_kernel<1, false>(const bf16_t*, const bf16_t*, const float*, bf16_t*, int, int, int);
-template __global__ void gemm_bias_act_glds_kernel<2, false>(const bf16_t*, const bf16_t*, const float*, bf16_t*, int, int, int);
-template __global__ void gemm_bias_act_glds_kernel<0, true>(const bf16_t*, const bf16_t*, const float*, bf16_t*, int, int, int);
+#define PANEL_INST(ACT, BT)                                                                          \
+  template __global__ void gemm_bias_act_panel_kernel<ACT, BT, 1>(const bf16_t*, const bf16_t*, const float*, bf16_t*, int, int, int, int); \
+  template __global__ void gemm_bias_act_panel_kernel<ACT, BT, 2>(const bf16_t*, const bf16_t*, const float*, bf16_t*, int, int, int, int); \
+  template __global__ void gemm_bias_act_panel_kernel<ACT, BT, 3>(const bf16_t*, const bf16_t*, const float*, bf16_t*, int, int, int, int); \
+  template __global__ void gemm_bias_act_panel_kernel<ACT, BT, 4>(const bf16_t*, const bf16_t*, const float*, bf16_t*, int, int, int, int); \
+  template __global__ void gemm_bias_act_panel_kernel<ACT, BT, 5>(const bf16_t*, const bf16_t*, const float*, bf16_t*, int, int, int, int); \
+  template __global__ void gemm_bias_act_panel_kernel<ACT, BT, 6>(const bf16_t*, const bf16_t*, const float*, bf16_t*, int, int, int, int);
+PANEL_INST(0, false)
+PANEL_INST(1, false)
+PANEL_INST(2, false)
+PANEL_INST(0, true)
+#undef PANEL_INST

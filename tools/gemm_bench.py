@@ -102,7 +102,42 @@ def bench_gemv(M, K, N, iters=50):
     err = (y[:256].float() - ref).abs().max().item()
     print(f"GEMV M={M:6d} K={K:3d} N={N:2d}: {dt*1e6:7.1f} us  {gb:6.0f} GB/s  maxerr {err:.3f}")
 
+# fwd / dX shapes of the row-panel kernel: the three hot training shapes, a
+# single n-tile (N = 64), the K = 384 single-W-buffer regime and the QP-label
+# row count
+PANEL_SHAPES = [(167936, 256, 256), (167936, 256, 128), (167936, 128, 128), (167936, 128, 64),
+                (167936, 64, 64), (167936, 384, 128), (503808, 128, 128), (503808, 256, 256)]
+
+
+def bench_fwd_bt(M, K, N, iters=50):
+    """Device time of Y = relu(X W + b) (K -> N) and of dX = dZ W^T at the same
+    layer (dZ is (M, N), W (N_out = K, K_red = N): reduction N, output K)."""
+    x = torch.randn(M, K, device="cuda").to(torch.bfloat16)
+    w = torch.randn(K, N, device="cuda").to(torch.bfloat16)
+    b = torch.randn(N, device="cuda")
+    fus = _event_us(lambda: _C.gemm_bias_act(x, w, b, 1), iters)
+    line = (f"FWD M={M:6d} K={K:3d} N={N:3d} {_C.gemm_path('fwd', M, K, N):8s}: {fus:7.1f} us "
+            f"{2 * M * K * N / fus / 1e6:6.1f} TF")
+    # BT with reduction K and output N: the mirror product of the same cost
+    dz = torch.randn(M, K, device="cuda").to(torch.bfloat16)
+    wt = torch.randn(N, K, device="cuda").to(torch.bfloat16)
+    bus = _event_us(lambda: _C.gemm_bt(dz, wt, dz, 0), iters)
+    line += (f" | BT {_C.gemm_path('bt', M, K, N, 0):8s}: {bus:7.1f} us "
+             f"{2 * M * K * N / bus / 1e6:6.1f} TF")
+    print(line, flush=True)
+
+
+def _parse_shapes(args):
+    return [tuple(int(v) for v in a.split(",")) for a in args]
+
+
 if __name__ == "__main__":
+    # `--panel [M,K,N ...]`: forward and dX times only, at the given shapes
+    # (default PANEL_SHAPES)
+    if len(sys.argv) > 1 and sys.argv[1] == "--panel":
+        for shape in _parse_shapes(sys.argv[2:]) or PANEL_SHAPES:
+            bench_fwd_bt(*shape)
+        sys.exit(0)
     for shape in [(167936, 256, 256), (167936, 32, 256), (167936, 256, 128),
                   (167936, 128, 128), (4096, 256, 256), (4096, 128, 256)]:
         bench(*shape)
