@@ -346,7 +346,8 @@ class GCBF(MultiAgentController):
         total, info = self._loss(mb, want_info)
         self.cbf_optim.zero_grad(set_to_none=False)
         self.actor_optim.zero_grad(set_to_none=False)
-        total.backward()
+        with ops.deferred_dw(total.device):  # flushed before the all-reduce
+            total.backward()
         if isinstance(self.cbf_optim, FusedAdamW):
             dp.allreduce_mean_flat([self.dp_gbuf])
             cbf_norm = self.cbf_optim.step()

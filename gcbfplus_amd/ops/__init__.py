@@ -13,6 +13,9 @@ Op inventory (kernel numbering follows SURVEY.md §2.7):
   fused_linear        K3/K4: MFMA GEMM + bias + activation, with autograd
                       (backward: transposed-B dX, deterministic split-M dW,
                       upstream-activation fold, direct grad accumulation)
+  deferred_dw         scope around backward(): the small-M dW/db of fused_linear
+                      run as grouped launches at its exit (GCBF_NO_DEFER_DW=1:
+                      immediate launches as outside the scope)
   masked_softmax_aggr K3/K4: per-receiver masked softmax + weighted message sum
   edge_msg_in         K2/K15: fused layer-0 GNN input build (+ analytic bwd);
                       mode 0 state diff, 1 DubinsCar, 2 CrazyFlie (node pre-pass)
@@ -30,6 +33,7 @@ Op inventory (kernel numbering follows SURVEY.md §2.7):
 """
 from __future__ import annotations
 
+import contextlib
 import os
 from typing import Optional
 
@@ -77,6 +81,39 @@ def _require_ext():
             "(or __graft_entry__.build())."
         )
     return ext
+
+
+# Deferred dW (ops.deferred_dw): a plain module flag, not a thread-local,
+# because backward of a device tensor runs on the autograd engine's thread.
+_DEFER_DW = False
+
+
+@contextlib.contextmanager
+def deferred_dw(device=None):
+    """Scope around a backward pass: the direct-accumulate dW/db calls of
+    fused_linear / fused_linear_onehot are queued (``_C.gemm_tn_defer``) and
+    run on exit as a few grouped launches (``_C.dw_flush``) instead of a
+    partial and a reduce launch per layer; every gradient keeps its bits. An
+    exception inside the scope discards the queue. No-op without the
+    extension, for a CPU ``device``, with GCBF_NO_DEFER_DW set, and when
+    nested."""
+    global _DEFER_DW
+    ext = _load_ext()
+    on_cpu = (torch.device(device).type == "cpu" if device is not None
+              else not torch.cuda.is_available())
+    if ext is None or on_cpu or _DEFER_DW or os.environ.get("GCBF_NO_DEFER_DW"):
+        yield
+        return
+    _DEFER_DW = True
+    try:
+        yield
+    except BaseException:
+        ext.dw_discard()
+        raise
+    else:
+        ext.dw_flush()
+    finally:
+        _DEFER_DW = False
 
 
 def _apply_act(y: Tensor, act: int) -> Tensor:
@@ -166,7 +203,10 @@ class _FusedLinearHIP(torch.autograd.Function):
             rg = ctx.row_gate
             if ctx.acc is not None:
                 wp, bp = ctx.acc
-                ext.gemm_tn_acc(x_bf, dz, yact, actin, wp.grad, bp.grad, rg)
+                if _DEFER_DW:
+                    ext.gemm_tn_defer(x_bf, dz, yact, actin, wp.grad, bp.grad, None, rg)
+                else:
+                    ext.gemm_tn_acc(x_bf, dz, yact, actin, wp.grad, bp.grad, rg)
             else:
                 dw, db = ext.gemm_tn(x_bf, dz, yact, actin, rg)  # f32 (K,N), (N,)
         if not ctx.has_bias:
@@ -230,8 +270,12 @@ class _FusedLinearOneHotHIP(torch.autograd.Function):
             dx = ext.gemm_bt(dz, w_bf3, yact, actin).to(ctx.x_dtype)
         if ctx.direct:
             w, b = ctx.params
-            ext.gemm_tn_acc2(x_bf, dz, yact, actin, w.grad[oh:], b.grad,
-                             w.grad[oh - 1], ctx.row_gate)
+            if _DEFER_DW:
+                ext.gemm_tn_defer(x_bf, dz, yact, actin, w.grad[oh:], b.grad,
+                                  w.grad[oh - 1], ctx.row_gate)
+            else:
+                ext.gemm_tn_acc2(x_bf, dz, yact, actin, w.grad[oh:], b.grad,
+                                 w.grad[oh - 1], ctx.row_gate)
         else:
             dw, db = ext.gemm_tn(x_bf, dz, yact, actin, ctx.row_gate)
             dw_full = torch.zeros(oh + dw.shape[0], dw.shape[1],

@@ -7,8 +7,10 @@
 #include <algorithm>
 #include <climits>
 #include <cstdint>
+#include <mutex>
 
 #include "crazyflie_consts.h"
+#include "dw_group.h"
 
 // kernel decls (defined in the .hip TUs)
 typedef __bf16 bf16_t_;
@@ -26,6 +28,8 @@ __global__ void dot_bias_act_kernel(const bf16_t_*, const bf16_t_*, const float*
 __global__ void act_bwd_kernel(const bf16_t_*, const bf16_t_*, bf16_t_*, long, int);
 template <int ACT>
 __global__ void gemm_tn_partial_kernel(const bf16_t_*, const bf16_t_*, const bf16_t_*, const bool*, float*, float*, int, int, int, int, int);
+__global__ void gemm_tn_partial_grouped_kernel(const TnPartialGroup);
+__global__ void reduce_dw_db_grouped_kernel(const DwReduceGroup);
 template <int ACT>
 __global__ void gemm_tn_partial2_kernel(const bf16_t_*, const bf16_t_*, const bf16_t_*, float*, float*, int, int, int, int, int);
 template <int ACT>
@@ -115,6 +119,12 @@ struct GemmPlan {
   long gk, gn, S;  // dW: output tile grid and split-M slab count
   bool remap;      // dW: XCD-aware 1-D launch decode
   int wbufs;       // row-panel kernel: W tile buffers in LDS (2, or 1 when 2 do not fit)
+  // dW through gemm_tn_defer: partial and reduce wait in the queue for the
+  // grouped launches of dw_flush (tn1), or both run at once as in gemm_tn_acc.
+  // Queueing the large-M (tn3) reduces as well measured 1.2% faster, inside
+  // three times the run-to-run spread, and was not kept (profiles/PROFILES.md
+  // "Round 5").
+  bool defer;
 };
 
 // Dynamic LDS a workgroup may request on the current device, as the runtime
@@ -167,6 +177,7 @@ static GemmPlan gemm_plan(GemmOp op, long M, long K, long N, long actin, bool ga
     if (p.remap) S = (S + 7) / 8 * 8;
     p.S = S;
     p.kernel = big ? (variant == 4 ? GK_TN4 : GK_TN2) : (variant == 3 ? GK_TN3 : GK_TN1);
+    p.defer = p.kernel == GK_TN1;
     return p;
   }
   const size_t b_image = (size_t)(K / 8) * 64 * 8 * sizeof(uint16_t);  // [K/8][64][8]
@@ -416,15 +427,26 @@ torch::Tensor act_bwd(torch::Tensor dy, torch::Tensor y, long act) {
 
 // (S,K,N) + (S,N) partials -> dW, db: dW blocks first (16-byte accesses when
 // K*N, the partial and dW allow), then the scalar db blocks
-static void launch_reduce_dw_db(const float* pw, const float* pb, float* dw, float* db,
-                                float* db2, long K, long N, long S, bool acc,
-                                hipStream_t stream) {
+static DwReduceProblem reduce_problem(const float* pw, const float* pb, float* dw, float* db,
+                                      float* db2, long K, long N, long S, bool acc,
+                                      long* nblocks) {
   const long KN = K * N;
   const bool vec = (KN & 3) == 0 && ((size_t)pw & 15) == 0 && ((size_t)dw & 15) == 0;
   const long per = vec ? 256 : 64;
   const long nbw = (KN + per - 1) / per, nbb = (N + 63) / 64;
-  hipLaunchKernelGGL(reduce_dw_db_kernel, dim3(nbw + nbb), dim3(256), 0, stream, pw, pb, dw,
-                     db, db2, KN, (int)N, (int)S, acc ? 1 : 0, vec ? 1 : 0, (int)nbw);
+  TORCH_CHECK(nbw + nbb <= INT_MAX, "reduce_dw_db: K*N too large");
+  *nblocks = nbw + nbb;
+  return DwReduceProblem{pw, pb, dw, db, db2, KN, (int)N, (int)S, acc ? 1 : 0, vec ? 1 : 0,
+                         (int)nbw, 0};
+}
+
+static void launch_reduce_dw_db(const float* pw, const float* pb, float* dw, float* db,
+                                float* db2, long K, long N, long S, bool acc,
+                                hipStream_t stream) {
+  long nb = 0;
+  const DwReduceProblem r = reduce_problem(pw, pb, dw, db, db2, K, N, S, acc, &nb);
+  hipLaunchKernelGGL(reduce_dw_db_kernel, dim3(nb), dim3(256), 0, stream, r.pw, r.pb, r.dW,
+                     r.db, r.db2, r.KN, r.N, r.S, r.acc, r.vec, r.nbw);
   C10_HIP_KERNEL_LAUNCH_CHECK();
 }
 
@@ -446,41 +468,56 @@ void reduce_dw_db(torch::Tensor partial, torch::Tensor db_partial, torch::Tensor
                       db2 ? db2->data_ptr<float>() : nullptr, K, N, S, acc, cur_stream());
 }
 
-std::vector<torch::Tensor> gemm_tn_impl(torch::Tensor x, torch::Tensor dz,
-                                        torch::Tensor yact, long actin,
-                                        torch::Tensor dw, torch::Tensor db, bool acc,
-                                        c10::optional<torch::Tensor> db2 = c10::nullopt,
-                                        c10::optional<torch::Tensor> rowgate = c10::nullopt) {
+// What gemm_tn_impl and gemm_tn_defer share: checks, plan and the partials.
+struct TnCall {
+  long M, K, N;
+  GemmPlan plan;
+  torch::Tensor partial, db_partial;  // (S, K, N), (S, N) f32
+  const bf16_t_* ya;
+  const bool* rg;
+};
+
+static TnCall tn_prepare(const torch::Tensor& x, const torch::Tensor& dz,
+                         const torch::Tensor& yact, long actin,
+                         const c10::optional<torch::Tensor>& rowgate) {
   CHECK_IN(x);
   CHECK_IN(dz);
-  long M = x.size(0), K = x.size(1), N = dz.size(1);
-  TORCH_CHECK(dz.size(0) == M);
-  const GemmPlan plan = gemm_plan(GEMM_TN, M, K, N, actin, rowgate.has_value());
+  TnCall c;
+  c.M = x.size(0), c.K = x.size(1), c.N = dz.size(1);
+  TORCH_CHECK(dz.size(0) == c.M);
+  c.plan = gemm_plan(GEMM_TN, c.M, c.K, c.N, actin, rowgate.has_value());
+  auto opts = x.options().dtype(torch::kFloat32);
+  c.partial = torch::empty({c.plan.S, c.K, c.N}, opts);
+  c.db_partial = torch::empty({c.plan.S, c.N}, opts);
+  c.ya = actin ? bfp(yact) : nullptr;
+  c.rg = nullptr;
+  if (rowgate) {
+    TORCH_CHECK(rowgate->is_contiguous() && rowgate->numel() == c.M
+                && rowgate->dtype() == torch::kBool);
+    c.rg = rowgate->data_ptr<bool>();
+  }
+  return c;
+}
+
+static void tn_launch_partial(TnCall& c, const torch::Tensor& x, const torch::Tensor& dz,
+                              long actin, hipStream_t stream) {
+  const GemmPlan& plan = c.plan;
   const long gk = plan.gk, gn = plan.gn, S = plan.S;
   const bool remap = plan.remap;
-
-  auto opts = x.options().dtype(torch::kFloat32);
-  auto partial = torch::empty({S, K, N}, opts);
-  auto db_partial = torch::empty({S, N}, opts);
-  auto stream = cur_stream();
-  const bf16_t_* ya = actin ? bfp(yact) : nullptr;
-  const bool* rg = nullptr;
-  if (rowgate) {
-    TORCH_CHECK(rowgate->is_contiguous() && rowgate->numel() == M
-                && rowgate->dtype() == torch::kBool);
-    rg = rowgate->data_ptr<bool>();
-  }
+  const long M = c.M, N = c.N, K = c.K;
+  const bf16_t_* ya = c.ya;
+  const bool* rg = c.rg;
   auto launch = [&](auto kernel) {
     hipLaunchKernelGGL(kernel, remap ? dim3(gk * gn * S) : dim3(gk, gn, S), dim3(256), 0,
-                       stream, bfp(x), bfp(dz), ya, rg, partial.data_ptr<float>(),
-                       db_partial.data_ptr<float>(), (int)M, (int)N, (int)K, (int)S,
+                       stream, bfp(x), bfp(dz), ya, rg, c.partial.data_ptr<float>(),
+                       c.db_partial.data_ptr<float>(), (int)M, (int)N, (int)K, (int)S,
                        remap ? 1 : 0);
     C10_HIP_KERNEL_LAUNCH_CHECK();
   };
   auto launch24 = [&](auto kernel) {  // kernels 2/4: no rowgate param
     hipLaunchKernelGGL(kernel, remap ? dim3(gk * gn * S) : dim3(gk, gn, S), dim3(256), 0,
-                       stream, bfp(x), bfp(dz), ya, partial.data_ptr<float>(),
-                       db_partial.data_ptr<float>(), (int)M, (int)N, (int)K, (int)S,
+                       stream, bfp(x), bfp(dz), ya, c.partial.data_ptr<float>(),
+                       c.db_partial.data_ptr<float>(), (int)M, (int)N, (int)K, (int)S,
                        remap ? 1 : 0);
     C10_HIP_KERNEL_LAUNCH_CHECK();
   };
@@ -501,9 +538,19 @@ std::vector<torch::Tensor> gemm_tn_impl(torch::Tensor x, torch::Tensor dz,
     else if (actin == 2) launch(gemm_tn_partial_kernel<2>);
     else launch(gemm_tn_partial_kernel<0>);
   }
-  launch_reduce_dw_db(partial.data_ptr<float>(), db_partial.data_ptr<float>(),
+}
+
+std::vector<torch::Tensor> gemm_tn_impl(torch::Tensor x, torch::Tensor dz,
+                                        torch::Tensor yact, long actin,
+                                        torch::Tensor dw, torch::Tensor db, bool acc,
+                                        c10::optional<torch::Tensor> db2 = c10::nullopt,
+                                        c10::optional<torch::Tensor> rowgate = c10::nullopt) {
+  TnCall c = tn_prepare(x, dz, yact, actin, rowgate);
+  auto stream = cur_stream();
+  tn_launch_partial(c, x, dz, actin, stream);
+  launch_reduce_dw_db(c.partial.data_ptr<float>(), c.db_partial.data_ptr<float>(),
                       dw.data_ptr<float>(), db.data_ptr<float>(),
-                      db2 ? db2->data_ptr<float>() : nullptr, K, N, S, acc, stream);
+                      db2 ? db2->data_ptr<float>() : nullptr, c.K, c.N, c.plan.S, acc, stream);
   return {dw, db};
 }
 
@@ -533,6 +580,176 @@ void gemm_tn_acc2(torch::Tensor x, torch::Tensor dz, torch::Tensor yact, long ac
   TORCH_CHECK(dw.size(0) == x.size(1) && dw.size(1) == dz.size(1) && db.size(0) == dz.size(1));
   TORCH_CHECK(db2.numel() == db.numel());
   gemm_tn_impl(x, dz, yact, actin, dw, db, true, db2, rowgate);
+}
+
+// ---------------------------------------------------------------------------
+// Deferred dW. The small-M (`tn1`) dW problems of one backward do not depend
+// on each other, yet as immediate calls each pays a partial launch and a
+// reduce launch that do almost no work. gemm_tn_defer queues them; dw_flush
+// runs the queue as grouped launches (gemm.hip), at most DW_GROUP_MAX
+// problems each: every partial kernel first, then every reduce.
+// The queue is process-global behind a mutex (backward of a device tensor
+// runs on the autograd engine's device thread, the flush on the caller's).
+// It keeps every operand, both partials and the destinations alive until the
+// flush; holding dz also keeps autograd from accumulating into it in place.
+// ---------------------------------------------------------------------------
+struct DwEntry {
+  TnPartialProblem tp;
+  long tp_blocks;
+  DwReduceProblem rp;
+  long rp_blocks;
+  std::vector<torch::Tensor> keep;
+  uintptr_t dst_lo[3], dst_hi[3];  // destination byte ranges (dW, db, db2)
+  int ndst;
+};
+
+static std::mutex g_dw_mutex;
+static std::vector<DwEntry> g_dw_queue;
+static hipStream_t g_dw_stream = nullptr;
+static long g_dw_launches[2] = {0, 0};  // grouped partial, grouped reduce
+
+// caller holds g_dw_mutex
+static void dw_flush_locked() {
+  if (g_dw_queue.empty()) return;
+  std::vector<DwEntry> q;
+  q.swap(g_dw_queue);  // a failed launch below still leaves the queue empty
+  const hipStream_t stream = g_dw_stream;
+  {
+    TnPartialGroup g{};
+    long nb = 0;
+    auto fire = [&]() {
+      if (g.n == 0) return;
+      g.start[g.n] = (int)nb;
+      hipLaunchKernelGGL(gemm_tn_partial_grouped_kernel, dim3(nb), dim3(256), 0, stream, g);
+      C10_HIP_KERNEL_LAUNCH_CHECK();
+      ++g_dw_launches[0];
+      g = TnPartialGroup{};
+      nb = 0;
+    };
+    for (const DwEntry& e : q) {
+      g.start[g.n] = (int)nb;
+      g.nblk[g.n] = (int)e.tp_blocks;
+      g.p[g.n] = e.tp;
+      // every problem starts at a multiple of 8, so a block's id within its
+      // problem keeps deciding its XCD (tn1_decode_remap)
+      nb += (e.tp_blocks + 7) / 8 * 8;
+      if (++g.n == DW_GROUP_MAX) fire();
+    }
+    fire();
+  }
+  {
+    DwReduceGroup g{};
+    long nb = 0;
+    auto fire = [&]() {
+      if (g.n == 0) return;
+      g.start[g.n] = (int)nb;
+      hipLaunchKernelGGL(reduce_dw_db_grouped_kernel, dim3(nb), dim3(256), 0, stream, g);
+      C10_HIP_KERNEL_LAUNCH_CHECK();
+      ++g_dw_launches[1];
+      g = DwReduceGroup{};
+      nb = 0;
+    };
+    for (const DwEntry& e : q) {
+      g.start[g.n] = (int)nb;
+      g.nblk[g.n] = (int)e.rp_blocks;
+      g.p[g.n] = e.rp;
+      nb += e.rp_blocks;
+      if (++g.n == DW_GROUP_MAX) fire();
+    }
+    fire();
+  }
+}
+
+void dw_flush() {
+  std::lock_guard<std::mutex> lock(g_dw_mutex);
+  dw_flush_locked();
+}
+
+long dw_pending() {
+  std::lock_guard<std::mutex> lock(g_dw_mutex);
+  return (long)g_dw_queue.size();
+}
+
+std::vector<long> dw_launch_counts() {
+  std::lock_guard<std::mutex> lock(g_dw_mutex);
+  return {g_dw_launches[0], g_dw_launches[1]};
+}
+
+// drop the queue without running it (the deferred gradients are lost)
+void dw_discard() {
+  std::lock_guard<std::mutex> lock(g_dw_mutex);
+  g_dw_queue.clear();
+}
+
+// gemm_tn_acc (db2 absent) / gemm_tn_acc2 with the launches deferred to
+// dw_flush where the plan says so; the rest runs immediately as there.
+void gemm_tn_defer(torch::Tensor x, torch::Tensor dz, torch::Tensor yact, long actin,
+                   torch::Tensor dw, torch::Tensor db,
+                   c10::optional<torch::Tensor> db2 = c10::nullopt,
+                   c10::optional<torch::Tensor> rowgate = c10::nullopt) {
+  auto f32 = [](const torch::Tensor& t) {
+    return t.is_cuda() && t.is_contiguous() && t.dtype() == torch::kFloat32;
+  };
+  TORCH_CHECK(f32(dw) && f32(db), "gemm_tn_defer: dw, db must be contiguous f32 on GPU");
+  TORCH_CHECK(x.dim() == 2 && dz.dim() == 2 && dw.dim() == 2);
+  TORCH_CHECK(dw.size(0) == x.size(1) && dw.size(1) == dz.size(1) && db.numel() == dz.size(1));
+  TORCH_CHECK(!db2 || (f32(*db2) && db2->numel() == db.numel()));
+  TORCH_CHECK(x.dtype() == torch::kBFloat16 && dz.dtype() == torch::kBFloat16);
+  TORCH_CHECK(actin >= 0 && actin <= 2);
+  if (actin) {
+    CHECK_IN(yact);
+    TORCH_CHECK(yact.dtype() == torch::kBFloat16 && yact.numel() == dz.numel());
+  }
+  TnCall c = tn_prepare(x, dz, yact, actin, rowgate);
+  const GemmPlan& plan = c.plan;
+  const hipStream_t stream = cur_stream();
+
+  DwEntry e;
+  e.ndst = 0;
+  auto add_dst = [&](const torch::Tensor& t) {
+    const uintptr_t lo = (uintptr_t)t.data_ptr<float>();
+    e.dst_lo[e.ndst] = lo;
+    e.dst_hi[e.ndst] = lo + (uintptr_t)t.numel() * sizeof(float);
+    ++e.ndst;
+  };
+  add_dst(dw);
+  add_dst(db);
+  if (db2) add_dst(*db2);
+
+  std::lock_guard<std::mutex> lock(g_dw_mutex);
+  if (!g_dw_queue.empty()) {
+    TORCH_CHECK(stream == g_dw_stream,
+                "gemm_tn_defer: entries are pending on another stream; dw_flush() first");
+    // accumulations into one destination keep the order of the calls
+    bool overlap = false;
+    for (const DwEntry& o : g_dw_queue)
+      for (int i = 0; i < o.ndst; ++i)
+        for (int j = 0; j < e.ndst; ++j)
+          overlap |= o.dst_lo[i] < e.dst_hi[j] && e.dst_lo[j] < o.dst_hi[i];
+    if (overlap) dw_flush_locked();
+  }
+  if (!plan.defer) {
+    tn_launch_partial(c, x, dz, actin, stream);
+    launch_reduce_dw_db(c.partial.data_ptr<float>(), c.db_partial.data_ptr<float>(),
+                        dw.data_ptr<float>(), db.data_ptr<float>(),
+                        db2 ? db2->data_ptr<float>() : nullptr, c.K, c.N, plan.S, true, stream);
+    return;
+  }
+  e.tp = TnPartialProblem{bfp(x), bfp(dz), c.ya, c.rg, c.partial.data_ptr<float>(),
+                          c.db_partial.data_ptr<float>(), (int)c.M, (int)c.N, (int)c.K,
+                          (int)plan.S, plan.remap ? 1 : 0, (int)actin, (int)plan.gk,
+                          (int)plan.gn};
+  e.tp_blocks = plan.gk * plan.gn * plan.S;
+  e.rp = reduce_problem(c.partial.data_ptr<float>(), c.db_partial.data_ptr<float>(),
+                        dw.data_ptr<float>(), db.data_ptr<float>(),
+                        db2 ? db2->data_ptr<float>() : nullptr, c.K, c.N, plan.S, true,
+                        &e.rp_blocks);
+  e.keep = {x, dz, c.partial, c.db_partial, dw, db};
+  if (actin) e.keep.push_back(yact);
+  if (rowgate) e.keep.push_back(*rowgate);
+  if (db2) e.keep.push_back(*db2);
+  if (g_dw_queue.empty()) g_dw_stream = stream;
+  g_dw_queue.push_back(std::move(e));
 }
 
 
@@ -707,6 +924,8 @@ torch::Tensor fused_adamw_step(torch::Tensor p, torch::Tensor g, torch::Tensor m
   CHECK_IN(g);
   CHECK_IN(m);
   CHECK_IN(v);
+  // a forgotten dw_flush must not drop gradients silently: the update reads g
+  dw_flush();
   long n = p.numel();
   auto stream = cur_stream();
   const int nb = 256;
@@ -1226,6 +1445,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_tn_acc", &gemm_tn_acc, py::arg("x"), py::arg("dz"), py::arg("yact"),
         py::arg("actin"), py::arg("dw"), py::arg("db"),
         py::arg("rowgate") = py::none());
+  m.def("gemm_tn_defer", &gemm_tn_defer,
+        "gemm_tn_acc / gemm_tn_acc2 with the small-M launches queued for dw_flush",
+        py::arg("x"), py::arg("dz"), py::arg("yact"), py::arg("actin"), py::arg("dw"),
+        py::arg("db"), py::arg("db2") = py::none(), py::arg("rowgate") = py::none());
+  m.def("dw_flush", &dw_flush, "run the deferred dW queue as grouped launches");
+  m.def("dw_pending", &dw_pending, "entries in the deferred dW queue");
+  m.def("dw_discard", &dw_discard, "drop the deferred dW queue without running it");
+  m.def("dw_launch_counts", &dw_launch_counts,
+        "(grouped partial, grouped reduce) launches issued by this process so far");
   m.def("softmax_aggr_fwd", &softmax_aggr_fwd);
   m.def("softmax_aggr_bwd", &softmax_aggr_bwd);
   m.def("mb_gather", &mb_gather, "fused 5-tensor minibatch gather (K18)");

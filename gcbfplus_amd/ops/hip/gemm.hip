@@ -20,7 +20,11 @@
 //   gemm_tn_partial + reduce  : dW = X^T @ dZ, deterministic split-M partials
 //                               + fixed-order reduction (no atomics), with
 //                               fused db and optional upstream-act fold.
+//   ..._grouped_kernel        : the small-M (tn1) partial and the reduce for
+//                               up to 16 independent problems per launch
+//                               (deferred dW: gemm_tn_defer / dw_flush).
 #include "common.h"
+#include "dw_group.h"
 
 
 // ---------------------------------------------------------------------------
@@ -328,46 +332,52 @@ __global__ void act_bwd_kernel(const bf16_t* __restrict__ dY, const bf16_t* __re
 // A-operand = X^T staged transposed in LDS (scalar transpose writes),
 // B-operand = dZ staged k-blocked like the forward GEMM.
 // ---------------------------------------------------------------------------
+// LDS of one tn1 block. The kernels own it and hand it to the body, so the
+// grouped kernel's three inlined ACT instantiations share one copy.
+struct Tn1Lds {
+  bf16_t sXT[64][72];    // [k][m] transposed X tile, pad >= BMR + 8
+  bf16_t sB[8][64][8];   // dZ tile, m-blocked
+  float sDb[4][64];      // db tree reduce (k0==0 blocks)
+};
+
+// XCD-aware placement (1-D launch, S % 8 == 0): all gk*gn blocks of one
+// split-M slab s get ids with id%8 == s%8 -> same XCD (dispatch places
+// block b on XCD b%8), so the X and dZ slab reads of the 2nd..24th block
+// hit that XCD's L2 instead of re-reading HBM from 6 different XCDs.
+// `id` is the block's id within its problem (the grouped kernel starts every
+// problem at a multiple of 8, which keeps id%8 the XCD there too).
+__device__ __forceinline__ void tn1_decode_remap(int id, int K, int N, int& kb, int& nb, int& s) {
+  const int gk = (K + 63) / 64, gn = (N + 63) / 64;
+  const int per = gk * gn;
+  const int rest = id >> 3;
+  s = (id & 7) + 8 * (rest / per);
+  const int j = rest % per;
+  kb = j / gn;
+  nb = j % gn;
+}
+
+// One block of the tn1 partial: output tile (kb, nb) of split-M slab s.
 template <int ACT>
-__launch_bounds__(256) __global__
-void gemm_tn_partial_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ dZ,
-                            const bf16_t* __restrict__ Yact,
-                            const bool* __restrict__ rowgate,  // null or (M,):
-                            // rows with gate=false contribute NOTHING to
-                            // dW/db (the dX path elsewhere stays ungated) —
-                            // implements per-sample stop-gradient of the
-                            // parameters (GCBF+ unlabeled h_dot rows)
-                            float* __restrict__ partial, float* __restrict__ db_partial,
-                            int M, int N, int K, int S, int remap) {
+__device__ __forceinline__
+void gemm_tn_partial_body(const bf16_t* __restrict__ X, const bf16_t* __restrict__ dZ,
+                          const bf16_t* __restrict__ Yact,
+                          const bool* __restrict__ rowgate,  // null or (M,):
+                          // rows with gate=false contribute NOTHING to
+                          // dW/db (the dX path elsewhere stays ungated) —
+                          // implements per-sample stop-gradient of the
+                          // parameters (GCBF+ unlabeled h_dot rows)
+                          float* __restrict__ partial, float* __restrict__ db_partial,
+                          int M, int N, int K, int S, int kb, int nb, int s, Tn1Lds& lds) {
   // 64x64 output tile, BMR=64 reduction steps with register-prefetch
   // staging (load tile t+1 into registers while tile t computes).
-  constexpr int BKDIM = 64, BN = 64, BMR = 64, TPAD = 72;  // pad >= BMR + 8
-  __shared__ bf16_t sXT[BKDIM][TPAD];   // [k][m] transposed X tile
-  __shared__ bf16_t sB[BMR / 8][BN][8]; // dZ tile, m-blocked
-  __shared__ float sDb[4][BN];          // db tree reduce (k0==0 blocks)
+  constexpr int BKDIM = 64, BN = 64, BMR = 64;
+  auto& sXT = lds.sXT;
+  auto& sB = lds.sB;
+  auto& sDb = lds.sDb;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int w = tid >> 6;
   const int wk = w >> 1, wn = w & 1;  // wave tile 32(K) x 32(N)
-  // XCD-aware placement (1-D launch, S % 8 == 0): all gk*gn blocks of one
-  // split-M slab s get ids with id%8 == s%8 -> same XCD (dispatch places
-  // block b on XCD b%8), so the X and dZ slab reads of the 2nd..24th block
-  // hit that XCD's L2 instead of re-reading HBM from 6 different XCDs.
-  int kb, nb, s;
-  if (remap) {
-    const int gk = (K + BKDIM - 1) / BKDIM, gn = (N + BN - 1) / BN;
-    const int per = gk * gn;
-    const int id = blockIdx.x;
-    const int rest = id >> 3;
-    s = (id & 7) + 8 * (rest / per);
-    const int j = rest % per;
-    kb = j / gn;
-    nb = j % gn;
-  } else {
-    kb = blockIdx.x;
-    nb = blockIdx.y;
-    s = blockIdx.z;
-  }
   const int k0 = kb * BKDIM;
   const int n0 = nb * BN;
 
@@ -495,6 +505,59 @@ void gemm_tn_partial_kernel(const bf16_t* __restrict__ X, const bf16_t* __restri
         if (krow < K) out[(long)krow * N + col] = acc[kf][nf][r];
       }
     }
+}
+
+template <int ACT>
+__launch_bounds__(256) __global__
+void gemm_tn_partial_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ dZ,
+                            const bf16_t* __restrict__ Yact, const bool* __restrict__ rowgate,
+                            float* __restrict__ partial, float* __restrict__ db_partial,
+                            int M, int N, int K, int S, int remap) {
+  __shared__ Tn1Lds lds;
+  int kb, nb, s;
+  if (remap) {
+    tn1_decode_remap(blockIdx.x, K, N, kb, nb, s);
+  } else {
+    kb = blockIdx.x;
+    nb = blockIdx.y;
+    s = blockIdx.z;
+  }
+  gemm_tn_partial_body<ACT>(X, dZ, Yact, rowgate, partial, db_partial, M, N, K, S, kb, nb, s, lds);
+}
+
+// Several independent tn1 problems in one launch (deferred-dW flush). A block
+// finds its problem by a uniform scan of the start table and runs the body
+// with its local id; per problem nothing changes (same tiles, slab ranges,
+// MFMA order), so every partial keeps its bits. Without the 1-D remap the
+// local id decodes x-fastest like the 3-D grid it replaces.
+__launch_bounds__(256) __global__
+void gemm_tn_partial_grouped_kernel(const TnPartialGroup g) {
+  __shared__ Tn1Lds lds;
+  const int bid = blockIdx.x;
+  int gi = 0;
+  for (int i = 1; i < g.n; ++i)
+    if (bid >= g.start[i]) gi = i;
+  const int id = bid - g.start[gi];
+  if (id >= g.nblk[gi]) return;  // alignment padding between problems
+  const TnPartialProblem& p = g.p[gi];
+  const int M = p.M, N = p.N, K = p.K, S = p.S;
+  int kb, nb, s;
+  if (p.remap) {
+    tn1_decode_remap(id, K, N, kb, nb, s);
+  } else {
+    kb = id % p.gk;
+    nb = (id / p.gk) % p.gn;
+    s = id / (p.gk * p.gn);
+  }
+  const bf16_t* X = (const bf16_t*)p.X;
+  const bf16_t* dZ = (const bf16_t*)p.dZ;
+  const bf16_t* Yact = (const bf16_t*)p.Yact;
+  if (p.act == 1)
+    gemm_tn_partial_body<1>(X, dZ, Yact, p.rowgate, p.partial, p.db_partial, M, N, K, S, kb, nb, s, lds);
+  else if (p.act == 2)
+    gemm_tn_partial_body<2>(X, dZ, Yact, p.rowgate, p.partial, p.db_partial, M, N, K, S, kb, nb, s, lds);
+  else
+    gemm_tn_partial_body<0>(X, dZ, Yact, p.rowgate, p.partial, p.db_partial, M, N, K, S, kb, nb, s, lds);
 }
 
 template __global__ void gemm_tn_partial_kernel<0>(const bf16_t*, const bf16_t*, const bf16_t*, const bool*, float*, float*, int, int, int, int, int);
@@ -1050,18 +1113,19 @@ template __global__ void gemm_tn_partial2_kernel<2>(const bf16_t*, const bf16_t*
 // db, 64 outputs each, always scalar.
 // acc != 0 accumulates (+=) into dW/db — used to write straight into the
 // optimizer's flat-gradient views, skipping autograd's AccumulateGrad adds.
-__launch_bounds__(256) __global__
-void reduce_dw_db_kernel(const float* __restrict__ pw, const float* __restrict__ pb,
-                         float* __restrict__ dW, float* __restrict__ db,
-                         float* __restrict__ db2,
-                         long KN, int N, int S, int acc, int vec, int nbw) {
-  __shared__ f32x4 sA[3][64];
+// `bid` is the block's id within its problem; sA is the block's LDS.
+__device__ __forceinline__
+void reduce_dw_db_body(const float* __restrict__ pw, const float* __restrict__ pb,
+                       float* __restrict__ dW, float* __restrict__ db,
+                       float* __restrict__ db2,
+                       long KN, int N, int S, int acc, int vec, int nbw, int bid,
+                       f32x4 (&sA)[3][64]) {
   const int lane = threadIdx.x & 63, j = threadIdx.x >> 6;
-  const bool is_db = (int)blockIdx.x >= nbw;  // block-uniform
+  const bool is_db = bid >= nbw;  // block-uniform
   const bool v4 = !is_db && vec;
   const float* src = is_db ? pb : pw;
   const long stride = is_db ? N : KN;
-  const long blk = is_db ? (long)blockIdx.x - nbw : (long)blockIdx.x;
+  const long blk = is_db ? (long)bid - nbw : (long)bid;
   const long off = (blk * 64 + lane) * (v4 ? 4 : 1);
   const bool live = off < stride;
   const int S4 = S & ~3;
@@ -1092,6 +1156,31 @@ void reduce_dw_db_kernel(const float* __restrict__ pw, const float* __restrict__
   // optional second db accumulation target (one-hot bias fold: the same db
   // flows into both bias.grad and kernel.grad[oh_row])
   if (is_db && db2 != nullptr) db2[off] += r;
+}
+
+__launch_bounds__(256) __global__
+void reduce_dw_db_kernel(const float* __restrict__ pw, const float* __restrict__ pb,
+                         float* __restrict__ dW, float* __restrict__ db,
+                         float* __restrict__ db2,
+                         long KN, int N, int S, int acc, int vec, int nbw) {
+  __shared__ f32x4 sA[3][64];
+  reduce_dw_db_body(pw, pb, dW, db, db2, KN, N, S, acc, vec, nbw, (int)blockIdx.x, sA);
+}
+
+// The reduces of several layers in one launch (deferred-dW flush): same table
+// scheme as gemm_tn_partial_grouped_kernel, the 16-byte or scalar variant
+// chosen per problem, the four summation chains of an output unchanged.
+__launch_bounds__(256) __global__
+void reduce_dw_db_grouped_kernel(const DwReduceGroup g) {
+  __shared__ f32x4 sA[3][64];
+  const int bid = blockIdx.x;
+  int gi = 0;
+  for (int i = 1; i < g.n; ++i)
+    if (bid >= g.start[i]) gi = i;
+  const int id = bid - g.start[gi];
+  if (id >= g.nblk[gi]) return;
+  const DwReduceProblem& p = g.p[gi];
+  reduce_dw_db_body(p.pw, p.pb, p.dW, p.db, p.db2, p.KN, p.N, p.S, p.acc, p.vec, p.nbw, id, sA);
 }
 
 // ---------------------------------------------------------------------------

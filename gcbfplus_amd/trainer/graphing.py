@@ -19,6 +19,7 @@ from typing import Optional
 
 import torch
 
+from .. import ops
 from ..utils.graph import GraphBatch
 from .data import FlatBatch
 
@@ -72,7 +73,10 @@ class GraphedMinibatchStep:
         algo = self.algo
         algo.dp_gbuf.zero_()  # both optimizers' gflats are slices of this
         total, _ = algo._loss(self.fb, want_info=False)
-        total.backward()
+        # the small-M dW launches of this backward run grouped, flushed here:
+        # inside the capture and before the optimizer step
+        with ops.deferred_dw(total.device):
+            total.backward()
         # single-GPU: optimizer inside the CAPTURE, but not in the warmup
         # bodies — repeated loss+backward+fused-optimizer sequences outside
         # the replayed graph intermittently page-fault on this ROCm pool

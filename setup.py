@@ -27,9 +27,11 @@ setup(
                 "gcbfplus_amd/ops/hip/bindings.hip",
             ],
             # headers: crazyflie_dyn.h is shared by env_step.hip and loss_prep.hip,
-            # crazyflie_edge.h by the mode-2 and jacobian kernels of edge_msg.hip
+            # crazyflie_edge.h by the mode-2 and jacobian kernels of edge_msg.hip,
+            # dw_group.h (grouped dW problem tables) by gemm.hip and bindings.hip
             depends=[
                 "gcbfplus_amd/ops/hip/common.h",
+                "gcbfplus_amd/ops/hip/dw_group.h",
                 "gcbfplus_amd/ops/hip/crazyflie_consts.h",
                 "gcbfplus_amd/ops/hip/crazyflie_dyn.h",
                 "gcbfplus_amd/ops/hip/crazyflie_edge.h",

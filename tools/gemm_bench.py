@@ -127,6 +127,43 @@ def bench_fwd_bt(M, K, N, iters=50):
     print(line, flush=True)
 
 
+# the six agent-level dW problems of one network's backward: (K, N, actin)
+GROUPED_SHAPES = [(128, 256, 1), (256, 256, 0), (256, 128, 0), (128, 256, 1), (256, 256, 0),
+                  (256, 1, 0)]
+
+
+def bench_grouped(M, gated, iters=50):
+    """Six immediate gemm_tn_acc calls (a partial and a reduce launch each)
+    against six gemm_tn_defer calls plus one dw_flush (grouped launches)."""
+    ops = []
+    for K, N, actin in GROUPED_SHAPES:
+        x = torch.randn(M, K, device="cuda").to(torch.bfloat16)
+        dy = torch.randn(M, N, device="cuda").to(torch.bfloat16)
+        y = torch.randn(M, N, device="cuda").relu().to(torch.bfloat16)
+        gate = (torch.rand(M, device="cuda") < 0.5) if gated else None
+        ops.append((x, dy, y if actin else dy, actin, torch.zeros(K, N, device="cuda"),
+                    torch.zeros(N, device="cuda"), gate))
+
+    def immediate():
+        for x, dy, y, actin, dw, db, gate in ops:
+            _C.gemm_tn_acc(x, dy, y, actin, dw, db, gate)
+
+    def deferred():
+        for x, dy, y, actin, dw, db, gate in ops:
+            _C.gemm_tn_defer(x, dy, y, actin, dw, db, None, gate)
+        _C.dw_flush()
+
+    # alternate the two arms so a drifting clock hits both
+    imm, dfr = [], []
+    for _ in range(3):
+        imm.append(_event_us(immediate, iters))
+        dfr.append(_event_us(deferred, iters))
+    i, d = sorted(imm)[1], sorted(dfr)[1]
+    print(f"GROUPED M={M:5d} gate={'half' if gated else 'none'}: 6 immediate {i:6.1f} us "
+          f"(12 launches) | 6 deferred + flush {d:6.1f} us (2 launches)  x{i / d:4.2f}",
+          flush=True)
+
+
 def _parse_shapes(args):
     return [tuple(int(v) for v in a.split(",")) for a in args]
 
@@ -137,6 +174,12 @@ if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "--panel":
         for shape in _parse_shapes(sys.argv[2:]) or PANEL_SHAPES:
             bench_fwd_bt(*shape)
+        sys.exit(0)
+    # `--grouped`: the small-M dW group of one network, immediate vs deferred
+    if len(sys.argv) > 1 and sys.argv[1] == "--grouped":
+        for M in (4096, 2048):
+            for gated in (False, True):
+                bench_grouped(M, gated)
         sys.exit(0)
     for shape in [(167936, 256, 256), (167936, 32, 256), (167936, 256, 128),
                   (167936, 128, 128), (4096, 256, 256), (4096, 128, 256)]:
