@@ -196,22 +196,34 @@ class GCBF(MultiAgentController):
             return None, self._env.edge_msg_in(graph, states)
         return self._edge_feats(graph, states), None
 
+    def _gnn_inputs(self, graph: GraphBatch, states: Optional[Tensor] = None):
+        """(edge_feats, msg_in) the networks are called with. gnn_layers >= 2
+        on the GPU takes the deep fused path (GNN._forward_deep: layer >= 1
+        inputs from ops.node_msg_in) from the fused layer-0 input alone;
+        GCBF_NO_FUSED_DEEP=1 keeps the torch edge-feature chain. Everything
+        else is ``_net_inputs``."""
+        st = graph.states if states is None else states
+        if (self.gnn_layers >= 2 and self._env.fused_edge and st.is_cuda
+                and ops.hip_available() and not os.environ.get("GCBF_NO_FUSED_DEEP")):
+            return None, self._env.edge_msg_in(graph, states)
+        return self._net_inputs(graph, states)
+
     def act(self, graph: GraphBatch) -> Tensor:
         if self.online_pol_refine:
             return self.online_policy_refinement(graph)
         with torch.no_grad():
-            e, mi = self._net_inputs(graph)
+            e, mi = self._gnn_inputs(graph)
             return 2 * self.actor(graph, e, msg_in=mi) + self._env.u_ref(graph)
 
     @torch.no_grad()
     def step(self, graph: GraphBatch) -> Tuple[Tensor, Tensor]:
-        e, mi = self._net_inputs(graph)
+        e, mi = self._gnn_inputs(graph)
         action = self.actor(graph, e, msg_in=mi)
         log_pi = torch.zeros_like(action)
         return 2 * action + self._env.u_ref(graph), log_pi
 
     def get_cbf(self, graph: GraphBatch) -> Tensor:
-        e, mi = self._net_inputs(graph)
+        e, mi = self._gnn_inputs(graph)
         return self.cbf(graph, e, msg_in=mi)
 
     def online_policy_refinement(self, graph: GraphBatch) -> Tensor:
@@ -304,7 +316,7 @@ class GCBF(MultiAgentController):
         action fed to forward_graph is the RAW actor output."""
         env = self._env
         g = mb.graph(env)
-        e, mi = self._net_inputs(g)
+        e, mi = self._gnn_inputs(g)
         h = self.cbf(g, e, msg_in=mi).squeeze(-1).reshape(-1)
         safe_m = mb.safe.reshape(-1)
         unsafe_m = mb.unsafe.reshape(-1)
@@ -314,7 +326,7 @@ class GCBF(MultiAgentController):
 
         action = self.actor(g, e, msg_in=mi)
         next_g = env.forward_graph(g, action)
-        e2, mi2 = self._net_inputs(next_g)
+        e2, mi2 = self._gnn_inputs(next_g)
         h_next = self.cbf(next_g, e2, msg_in=mi2).squeeze(-1).reshape(-1)
         h_dot = (h_next - h) / env.dt
         val = torch.relu(-h_dot - self.alpha * h + self.eps)

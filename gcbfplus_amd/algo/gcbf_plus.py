@@ -205,7 +205,7 @@ class GCBFPlus(GCBF):
         env = self._env
         g = mb.graph(env)
         B = g.batch_size
-        e, mi = self._net_inputs(g)
+        e, mi = self._gnn_inputs(g)
         safe_m = mb.safe.reshape(-1)
         unsafe_m = mb.unsafe.reshape(-1)
 
@@ -228,7 +228,7 @@ class GCBFPlus(GCBF):
             mask=torch.cat([g.mask, g.mask]),
             n_agents=g.n_agents, n_rays=g.n_rays,
         )
-        e_big, mi_big = self._net_inputs(big)
+        e_big, mi_big = self._gnn_inputs(big)
         gated = (g.states.is_cuda and ops.hip_available() and self.gnn_layers == 1
                  and not os.environ.get("GCBF_NO_GATED_NG"))
         if gated:

@@ -60,8 +60,22 @@ class GNNLayer(nn.Module):
         self.attn_out = Dense(hid_aggr[-1], 1)
         self.update_mlp = MLP(node_dim + msg_dim, hid_update, act="relu", act_final=False)
         self.update_out = Dense(hid_update[-1], out_dim)
+        self.node_dim = node_dim
+        self.edge_dim = edge_dim
         self.msg_dim = msg_dim
         self.out_dim = out_dim
+
+    def const_node_update(self, c: Tensor) -> Tensor:
+        """Update of nodes that receive no message (goal and lidar-hit nodes:
+        aggr == 0), c (rows, node_dim) -> (rows, out_dim): update_out(
+        update_mlp([c, 0])) in plain f32 torch on the master parameters.
+        Broadcast-multiply-sum rather than a BLAS call: two rows, and legal in
+        a stream capture whatever the BLAS workspace state."""
+        h = c
+        for l in list(self.update_mlp.layers) + [self.update_out]:
+            w = l.kernel[: h.shape[-1]]  # first Dense: the aggr rows meet zeros
+            h = ops._apply_act((h.unsqueeze(-1) * w).sum(-2) + l.bias, l.act)
+        return h
 
     def forward(
         self,
@@ -142,9 +156,19 @@ class GNN(nn.Module):
         B = graph.batch_size
         N, R, V = graph.n_agents, graph.n_rays, graph.n_nodes
         n_layers = len(self.layers)
+        if row_gate is not None:
+            # Stays single-layer ON PURPOSE: with two rounds, agent i's output
+            # depends on the layer-0 rows of its neighbours, and a labelled
+            # neighbour needs parameter gradients from those SAME rows. A
+            # per-row gate cannot express that stop-gradient, so do not lift
+            # this for the deep path.
+            assert n_layers == 1, "row_gate requires gnn_layers == 1"
         if edge_feats is None:
-            assert msg_in0 is not None and n_layers == 1, \
-                "edge_feats required unless a fused msg_in0 covers the single layer"
+            assert msg_in0 is not None, "edge_feats required unless a fused msg_in0 is given"
+            if n_layers >= 2:
+                assert node_feats is None and self.node_dim == 3, \
+                    "the deep fused path takes the constant one-hot node features"
+                return self._forward_deep(graph, msg_in0)
             device = msg_in0.device
         else:
             device = edge_feats.device
@@ -153,14 +177,46 @@ class GNN(nn.Module):
             node_feats = one_hot_node_feats(B, N, R, device, torch.float32)
         send_idx = sender_index(N, R, device)
         x = node_feats
-        if row_gate is not None:
-            assert n_layers == 1, "row_gate requires gnn_layers == 1"
         for i, layer in enumerate(self.layers):
             last = i == n_layers - 1
             x = layer(x, edge_feats, graph.mask, send_idx, agents_only=last,
                       msg_in=msg_in0 if i == 0 else None,
                       onehot_nodes=onehot and i == 0, row_gate=row_gate)
         return x  # (B, N, out_dim)
+
+    def _forward_deep(self, graph: GraphBatch, X0: Tensor) -> Tensor:
+        """n_layers >= 2 from the fused layer-0 input X0 alone. Goal and
+        lidar-hit nodes never receive a message (their aggr is zero at every
+        layer), so after layer l their features are two constant rows that
+        depend on the parameters only; every layer runs its update MLP over
+        the B*N agent rows instead of all V nodes, and the input of layer
+        l >= 1 is the gather ``ops.node_msg_in`` (edge columns of X0 | sender
+        agent row or constant | receiver row)."""
+        B, N, R = graph.batch_size, graph.n_agents, graph.n_rays
+        send_idx = sender_index(N, R, X0.device)
+        x = self.layers[0](one_hot_node_feats(B, N, R, X0.device, torch.float32), None,
+                           graph.mask, send_idx, agents_only=True, msg_in=X0,
+                           onehot_nodes=True)  # (B, N, msg_dim)
+        c = _const_node_onehots(X0.device)  # (2, 3): goal, lidar hit
+        for prev, layer in zip(self.layers[:-1], self.layers[1:]):
+            c = prev.const_node_update(c)
+            xa = x.to(torch.bfloat16) if x.is_cuda else x
+            msg_in = ops.node_msg_in(X0, xa, c, layer.edge_dim, R)
+            x = layer(x, None, graph.mask, send_idx, agents_only=True, msg_in=msg_in)
+        return x  # (B, N, out_dim)
+
+
+def _const_node_onehots(device) -> Tensor:
+    """(2, 3) f32 one-hots of a goal node (010) and a lidar-hit node (100).
+    Cached per device, built without a host-to-device copy."""
+    key = ("const", str(device))
+    c = _ONEHOT_CACHE.get(key)
+    if c is None:
+        c = torch.zeros(2, 3, device=device)
+        c[0, 1] = 1.0
+        c[1, 0] = 1.0
+        _ONEHOT_CACHE[key] = c
+    return c
 
 
 def one_hot_node_feats(B: int, N: int, R: int, device, dtype=torch.float32) -> Tensor:

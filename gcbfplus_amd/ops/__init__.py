@@ -19,6 +19,8 @@ Op inventory (kernel numbering follows SURVEY.md §2.7):
   masked_softmax_aggr K3/K4: per-receiver masked softmax + weighted message sum
   edge_msg_in         K2/K15: fused layer-0 GNN input build (+ analytic bwd);
                       mode 0 state diff, 1 DubinsCar, 2 CrazyFlie (node pre-pass)
+  node_msg_in         fused layer >= 1 GNN input (gnn_layers >= 2): edge columns of
+                      the layer-0 input | sender agent / constant row | receiver
   crazyflie_edge_jac  dh/d(edge feats) -> dh_i/dx_j for the CrazyFlie QP labels
   raytrace_rect       K1: 2D LiDAR fan vs rectangle set (no grad)
   gcbf_plus_loss      K10: all GCBF+ hinge losses + metrics in one kernel pair
@@ -484,6 +486,75 @@ def edge_msg_in(states: Tensor, n_agents: int, n_rays: int, pos_dim: int,
     if k_pad > K:
         out = torch.cat([out, out.new_zeros(B, n, D, k_pad - K)], dim=-1)
     return out
+
+
+# --------------------------------------------------------------------------
+# node_msg_in: fused GNN input of layer >= 1 (deep path, gnn_layers >= 2)
+# --------------------------------------------------------------------------
+class _NodeMsgInHIP(torch.autograd.Function):
+    """Operands go to the extension as they are: it refuses a wrong dtype or
+    layout instead of converting it on the quiet."""
+
+    @staticmethod
+    def forward(ctx, X0: Tensor, xa: Tensor, c: Tensor, E: int, n_rays: int, k_pad: int):
+        ext = _require_ext()
+        X1 = ext.node_msg_in_fwd(X0, xa, c, E, n_rays, k_pad)
+        ctx.meta = (E, xa.shape[-1], n_rays, X0.shape[-1])
+        return X1
+
+    @staticmethod
+    def backward(ctx, dX1: Tensor):
+        ext = _require_ext()
+        E, F, n_rays, kp0 = ctx.meta
+        dX0, dxa, dc = ext.node_msg_in_bwd(dX1.contiguous().to(torch.bfloat16), E, F,
+                                           n_rays, kp0)
+        # xa is bf16: its gradient takes the input's dtype, as autograd requires
+        return dX0, dxa.to(torch.bfloat16), dc, None, None, None
+
+
+def node_msg_in(X0: Tensor, xa: Tensor, c: Tensor, E: int,
+                n_rays: Optional[int] = None, k_pad: Optional[int] = None) -> Tensor:
+    """Fused input of GNN layer >= 1 on the deep path: per edge slot (b, i, d)
+    [X0[b,i,d,:E] | s | xa[b,i] | 0 pad], (B, N, D, KP1), KP1 = ceil32(E + 2F);
+    s = xa[b,d] for d < N (sender is agent d), c[0] for d == N (the goal node)
+    and c[1] for d > N (a lidar hit node). Goal and hit nodes never receive a
+    message, so their features are the two constant rows c (2, F).
+
+    X0 (B, N, D, KP0) is the layer-0 input of ``edge_msg_in`` (its first E
+    columns are the edge features in every mode); xa (B, N, F) the previous
+    layer's agent features. ``n_rays`` defaults to D - N - 1.
+
+    GPU: bf16 HIP kernel pair, X0/xa bf16 and c f32 (anything else is refused
+    before a launch); the backward sums in a fixed order without atomics.
+    CPU: composed torch in X0's dtype, differentiable.
+    """
+    B, N, D, _ = X0.shape
+    F = xa.shape[-1]
+    if n_rays is None:
+        n_rays = D - N - 1
+    if k_pad is None:
+        k_pad = (E + 2 * F + 31) // 32 * 32
+    if X0.is_cuda:
+        return _NodeMsgInHIP.apply(X0, xa, c, E, n_rays, k_pad)
+    if D != N + 1 + n_rays or n_rays < 0:
+        raise ValueError(f"node_msg_in: D = {D} is not N + 1 + R for N = {N}, R = {n_rays}")
+    if not E + 2 * F <= k_pad < E + 2 * F + 32:
+        raise ValueError(f"node_msg_in: k_pad = {k_pad} does not fit E + 2F = {E + 2 * F}")
+    xa = xa.to(X0.dtype)
+    c = c.to(X0.dtype)
+    sender = torch.cat(
+        [
+            xa[:, None, :, :].expand(B, N, N, F),
+            c[0].expand(B, N, 1, F),
+            c[1].expand(B, N, n_rays, F),
+        ],
+        dim=2,
+    )
+    recv = xa[:, :, None, :].expand(B, N, D, F)
+    parts = [X0[..., :E], sender, recv]
+    if k_pad > E + 2 * F:
+        parts.append(X0.new_zeros(B, N, D, k_pad - E - 2 * F))
+    return torch.cat(parts, dim=-1)
 
 
 def crazyflie_edge_jac(states: Tensor, ge: Tensor, n_agents: int, n_rays: int,

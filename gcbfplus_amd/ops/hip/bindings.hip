@@ -61,6 +61,13 @@ __global__ void crazyflie_edge_state_kernel(const float*, float*, long);
 __global__ void edge_msg_in_fwd_cf_kernel(const float*, bf16_t_*, int, int, int, float);
 __global__ void edge_msg_in_bwd_cf_kernel(const float*, const float*, const bf16_t_*, float*, int, int, int, float);
 __global__ void crazyflie_edge_jac_kernel(const float*, const float*, const float*, float*, int, int, int, float);
+template <int W>
+__global__ void node_msg_in_fwd_kernel(const bf16_t_*, const bf16_t_*, const float*, bf16_t_*, long, int, int, int, int, int, int);
+template <int W>
+__global__ void node_msg_in_bwd_dx0_kernel(const bf16_t_*, bf16_t_*, long, int, int, int);
+template <int W>
+__global__ void node_msg_in_bwd_gather_kernel(const bf16_t_*, float*, float*, long, int, int, int, int, int);
+__global__ void node_msg_in_dc_reduce_kernel(const float*, float*, long, int);
 __global__ void gcbf_loss_fwd_kernel(const float*, const float*, const float*, const float*, const float*, const bool*, const bool*, float*, long, int, float, float, float, float, float, float, float);
 __global__ void di_loss_prep_fwd_kernel(const float*, const float*, const float*, float*, float*,
                                         int, int, int, float, float, float, float);
@@ -1140,6 +1147,102 @@ torch::Tensor crazyflie_edge_jac(torch::Tensor states, torch::Tensor ge, long N,
   return hx;
 }
 
+// ---------------------------------------------------------------------------
+// node_msg_in: fused GNN input of layer >= 1 (node_msg.hip). Every operand is
+// checked before any launch; no host sync, no descriptor buffers (both
+// directions are legal inside a stream capture).
+// ---------------------------------------------------------------------------
+static void check_node_msg_dims(long N, long D, long R, long E, long F, long KP0, long KP1,
+                                const char* who) {
+  TORCH_CHECK(N >= 1 && R >= 0 && D == N + 1 + R, who, ": D = ", D,
+              " is not N + 1 + R for N = ", N, ", R = ", R);
+  TORCH_CHECK(F >= 8 && F % 8 == 0, who, ": F must be a positive multiple of 8, got ", F);
+  TORCH_CHECK(KP0 >= 32 && KP0 % 32 == 0, who, ": KP0 must be a multiple of 32, got ", KP0);
+  TORCH_CHECK(KP1 >= 32 && KP1 % 32 == 0, who, ": KP1 must be a multiple of 32, got ", KP1);
+  TORCH_CHECK(E >= 1 && E <= KP0, who, ": need 1 <= E <= KP0, got E = ", E, ", KP0 = ", KP0);
+  TORCH_CHECK(E + 2 * F <= KP1 && KP1 < E + 2 * F + 32, who, ": KP1 = ", KP1,
+              " is not E + 2F = ", E + 2 * F, " padded to the next multiple of 32");
+  TORCH_CHECK(std::max(std::max(N, D), std::max(KP0, KP1)) <= INT_MAX, who,
+              ": dimension exceeds int range");
+}
+
+static void check_node_msg_bf16(const torch::Tensor& t, const char* name, const char* who) {
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.scalar_type() == torch::kBFloat16 &&
+                  b128_aligned(t),
+              who, ": ", name, " must be a contiguous, 16 B aligned bf16 GPU tensor");
+}
+
+torch::Tensor node_msg_in_fwd(torch::Tensor X0, torch::Tensor xa, torch::Tensor c, long E,
+                              long R, long KP1) {
+  const char* who = "node_msg_in_fwd";
+  check_node_msg_bf16(X0, "X0", who);
+  check_node_msg_bf16(xa, "xa", who);
+  TORCH_CHECK(c.is_cuda() && c.is_contiguous() && c.scalar_type() == torch::kFloat32, who,
+              ": c must be a contiguous f32 GPU tensor");
+  TORCH_CHECK(xa.device() == X0.device() && c.device() == X0.device(), who,
+              ": operands on different devices");
+  TORCH_CHECK(X0.dim() == 4 && xa.dim() == 3, who, ": X0 must be (B, N, D, KP0), xa (B, N, F)");
+  long B = X0.size(0), N = X0.size(1), D = X0.size(2), KP0 = X0.size(3), F = xa.size(2);
+  TORCH_CHECK(xa.size(0) == B && xa.size(1) == N, who, ": xa is not (B, N, F) of X0's B, N");
+  TORCH_CHECK(c.dim() == 2 && c.size(0) == 2 && c.size(1) == F, who, ": c must be (2, F)");
+  check_node_msg_dims(N, D, R, E, F, KP0, KP1, who);
+  auto X1 = torch::empty({B, N, D, KP1}, X0.options());
+  long rows = B * N * D;
+  if (rows == 0) return X1;
+  long total = rows * (KP1 / 8);
+  if (E % 2 == 0) {
+    hipLaunchKernelGGL(node_msg_in_fwd_kernel<2>, edge_grid(total), dim3(256), 0, cur_stream(),
+                       bfp(X0), bfp(xa), c.data_ptr<float>(), bfp_mut(X1), rows, (int)N,
+                       (int)D, (int)E, (int)F, (int)KP0, (int)KP1);
+  } else {
+    hipLaunchKernelGGL(node_msg_in_fwd_kernel<1>, edge_grid(total), dim3(256), 0, cur_stream(),
+                       bfp(X0), bfp(xa), c.data_ptr<float>(), bfp_mut(X1), rows, (int)N,
+                       (int)D, (int)E, (int)F, (int)KP0, (int)KP1);
+  }
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return X1;
+}
+
+// dX1 (B,N,D,KP1) bf16 -> (dX0 (B,N,D,KP0) bf16, dxa (B,N,F) f32, dc (2,F) f32)
+std::vector<torch::Tensor> node_msg_in_bwd(torch::Tensor dX1, long E, long F, long R,
+                                           long KP0) {
+  const char* who = "node_msg_in_bwd";
+  check_node_msg_bf16(dX1, "dX1", who);
+  TORCH_CHECK(dX1.dim() == 4, who, ": dX1 must be (B, N, D, KP1)");
+  long B = dX1.size(0), N = dX1.size(1), D = dX1.size(2), KP1 = dX1.size(3);
+  check_node_msg_dims(N, D, R, E, F, KP0, KP1, who);
+  auto f32 = dX1.options().dtype(torch::kFloat32);
+  auto dX0 = torch::empty({B, N, D, KP0}, dX1.options());
+  auto dxa = torch::empty({B, N, F}, f32);
+  long BN = B * N, rows = BN * D;
+  if (rows == 0) return {dX0, dxa, torch::zeros({2, F}, f32)};
+  auto dc = torch::empty({2, F}, f32);
+  auto part = torch::empty({BN, 2, F}, f32);
+  const int W = (E % 2 == 0) ? 2 : 1;
+  long t0 = rows * (KP0 / 8), t1 = BN * (F / W);
+  if (W == 2) {
+    hipLaunchKernelGGL(node_msg_in_bwd_dx0_kernel<2>, edge_grid(t0), dim3(256), 0,
+                       cur_stream(), bfp(dX1), bfp_mut(dX0), rows, (int)E, (int)KP0, (int)KP1);
+    C10_HIP_KERNEL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(node_msg_in_bwd_gather_kernel<2>, edge_grid(t1), dim3(256), 0,
+                       cur_stream(), bfp(dX1), dxa.data_ptr<float>(), part.data_ptr<float>(),
+                       BN, (int)N, (int)D, (int)E, (int)F, (int)KP1);
+  } else {
+    hipLaunchKernelGGL(node_msg_in_bwd_dx0_kernel<1>, edge_grid(t0), dim3(256), 0,
+                       cur_stream(), bfp(dX1), bfp_mut(dX0), rows, (int)E, (int)KP0, (int)KP1);
+    C10_HIP_KERNEL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(node_msg_in_bwd_gather_kernel<1>, edge_grid(t1), dim3(256), 0,
+                       cur_stream(), bfp(dX1), dxa.data_ptr<float>(), part.data_ptr<float>(),
+                       BN, (int)N, (int)D, (int)E, (int)F, (int)KP1);
+  }
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  hipLaunchKernelGGL(node_msg_in_dc_reduce_kernel, dim3((unsigned)((2 * F + 15) / 16)),
+                     dim3(256), 0, cur_stream(), part.data_ptr<float>(), dc.data_ptr<float>(),
+                     BN, (int)(2 * F));
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return {dX0, dxa, dc};
+}
+
 torch::Tensor gcbf_loss_fwd(torch::Tensor h, torch::Tensor h_next, torch::Tensor h_ng,
                             torch::Tensor action, torch::Tensor u_qp, torch::Tensor safe,
                             torch::Tensor unsafe, double dt, double alpha, double eps,
@@ -1424,6 +1527,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("edge_msg_in_fwd", &edge_msg_in_fwd);
   m.def("edge_msg_in_bwd", &edge_msg_in_bwd);
   m.def("crazyflie_edge_jac", &crazyflie_edge_jac);
+  m.def("node_msg_in_fwd", &node_msg_in_fwd,
+        "layer >= 1 GNN input [X0[:E] | sender | recv | 0 pad], bf16 (B, N, D, KP1)",
+        py::arg("X0"), py::arg("xa"), py::arg("c"), py::arg("E"), py::arg("R"),
+        py::arg("KP1"));
+  m.def("node_msg_in_bwd", &node_msg_in_bwd,
+        "dX1 -> (dX0 bf16, dxa f32, dc f32), fixed summation order, no atomics",
+        py::arg("dX1"), py::arg("E"), py::arg("F"), py::arg("R"), py::arg("KP0"));
   m.def("fused_adamw_step", &fused_adamw_step,
         "flat-buffer global-norm-clip AdamW with finite guard (K13)");
   m.def("proxqp_solve", &proxqp_solve_hip, "batched dense QP, one wave per problem (K11)");
