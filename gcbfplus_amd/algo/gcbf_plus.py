@@ -212,7 +212,25 @@ class GCBFPlus(GCBF):
         # action = 2*actor + u_ref (the deployed policy); h and h_next in ONE
         # batched CBF forward (2B graphs): halves the GEMM call count and
         # doubles M for better CU fill
-        raw = self.actor(g, e, msg_in=mi)
+        gated = (g.states.is_cuda and ops.hip_available() and self.gnn_layers == 1
+                 and not os.environ.get("GCBF_NO_GATED_NG"))
+        wgate = None
+        if gated:
+            labeled = (mb.safe | mb.unsafe)  # (B, N)
+            wgate = torch.cat([torch.ones_like(labeled), labeled], dim=0)
+        # g, next_g and the actor share g.mask: ONE compaction of the doubled
+        # mask serves the batched CBF call, and its prefix (the first B*N
+        # receivers) the actor. A function of shapes only: a captured
+        # minibatch keeps its path.
+        mask_big = torch.cat([g.mask, g.mask])
+        compact = None
+        if (mi is not None and g.states.is_cuda and ops.hip_available()
+                and self.gnn_layers == 1 and ops.edge_compact_wanted(mask_big.numel())):
+            compact = ops.EdgeCompact.build(mask_big, row_gate=wgate,
+                                            prefix_recv=B * g.n_agents)
+        ckw = {} if compact is None else {"compact": compact}
+        akw = {} if compact is None else {"compact": compact.prefix()}
+        raw = self.actor(g, e, msg_in=mi, **akw)
         prep = env.loss_prep(g, raw) if hasattr(env, "loss_prep") else None
         if prep is not None:
             # fused K16 kernel: u_ref + action clamp + euler + [cur; next]
@@ -225,12 +243,10 @@ class GCBFPlus(GCBF):
             big_states = torch.cat([g.states, next_g.states])
         big = GraphBatch(
             states=big_states,
-            mask=torch.cat([g.mask, g.mask]),
+            mask=mask_big,
             n_agents=g.n_agents, n_rays=g.n_rays,
         )
         e_big, mi_big = self._gnn_inputs(big)
-        gated = (g.states.is_cuda and ops.hip_available() and self.gnn_layers == 1
-                 and not os.environ.get("GCBF_NO_GATED_NG"))
         if gated:
             # The stop-gradient CBF evaluation has IDENTICAL VALUES to h_next
             # (same params — stop_gradient only cuts the param backward). So:
@@ -240,18 +256,15 @@ class GCBFPlus(GCBF):
             # next_g's states) flows for ALL rows, exactly as the reference's
             # two-evaluation scheme (gcbf_plus.py:398-408) — and one full
             # B-sized CBF forward+backward per minibatch disappears.
-            N = self.n_agents
-            labeled = (mb.safe | mb.unsafe)  # (B, N)
-            wgate = torch.cat([torch.ones_like(labeled), labeled], dim=0)
             h_both = self.cbf(big, e_big, msg_in=mi_big,
-                              row_gate=wgate).squeeze(-1)  # (2B, N)
+                              row_gate=wgate, **ckw).squeeze(-1)  # (2B, N)
             h = h_both[:B].reshape(-1)
             h_next = h_both[B:].reshape(-1)
             h_next_ng = h_next  # same tensor: the loss kernel's h_ng cotangent
             # (unlabeled rows) and h_next cotangent (labeled rows) are
             # row-disjoint and autograd sums them into one backward
         else:
-            h_both = self.cbf(big, e_big, msg_in=mi_big).squeeze(-1)  # (2B, N)
+            h_both = self.cbf(big, e_big, msg_in=mi_big, **ckw).squeeze(-1)  # (2B, N)
             h = h_both[:B].reshape(-1)
             h_next = h_both[B:].reshape(-1)
 

@@ -25,9 +25,10 @@ class CBFNet(nn.Module):
         self.out = Dense(256, 1, act="tanh")
 
     def forward(self, graph: GraphBatch, edge_feats: Tensor, msg_in=None,
-                row_gate=None) -> Tensor:
+                row_gate=None, compact=None) -> Tensor:
         """-> h: (B, N, 1) in [-1, 1]. row_gate (B, N) bool: per-agent
-        parameter stop-gradient (see ops.fused_linear)."""
-        x = self.gnn(graph, edge_feats, msg_in0=msg_in, row_gate=row_gate)
+        parameter stop-gradient (see ops.fused_linear). compact: the
+        ops.EdgeCompact of graph.mask (edge level on active slots only)."""
+        x = self.gnn(graph, edge_feats, msg_in0=msg_in, row_gate=row_gate, compact=compact)
         ag = None if row_gate is None else row_gate.reshape(-1).contiguous()
         return self.out(self.head(x, ag), ag)

@@ -87,21 +87,40 @@ class GNNLayer(nn.Module):
         msg_in: Tensor = None,  # optional fused (B, N, D, K[pad]) input
         onehot_nodes: bool = False,  # node_feats ARE the constant one-hots
         row_gate: Tensor = None,  # (B, N) bool param stop-grad mask
+        compact: "ops.EdgeCompact" = None,  # active slots of `mask` (GPU, fused msg_in)
     ) -> Tensor:
         B, V, F = node_feats.shape
         N, D = mask.shape[1], mask.shape[2]
         eg = ag = None  # edge-level / agent-level flat gates
         if row_gate is not None:
-            eg = row_gate[:, :, None].expand(B, N, D).reshape(-1).contiguous()
+            if compact is None:
+                eg = row_gate[:, :, None].expand(B, N, D).reshape(-1).contiguous()
             ag = row_gate.reshape(-1).contiguous()
-        if msg_in is None:
-            flat_idx = send_idx.reshape(-1)  # (N*D,)
-            sender = node_feats[:, flat_idx].reshape(B, N, D, F)
-            recv = node_feats[:, :N, None, :].expand(B, N, D, F)
-            msg_in = torch.cat([edge_feats, sender, recv], dim=-1)
-        msg = self.msg_out(self.msg_mlp(msg_in, eg), eg)  # (B,N,D,msg_dim)
-        gate = self.attn_out(self.attn_mlp(msg, eg), eg).squeeze(-1)  # (B,N,D)
-        aggr = ops.masked_softmax_aggr(gate, msg, mask)  # (B,N,msg_dim)
+        if compact is not None:
+            # Edge level on the active slots only: a masked slot has attention
+            # 0, so its row reaches no output and no gradient. Compact rows
+            # keep the slot order, every buffer keeps its worst-case size and
+            # the kernels read the row count on the device (ops.EdgeCompact).
+            assert msg_in is not None and compact.n_recv == B * N and compact.D == D, \
+                "compact needs the fused msg_in of the mask it was built from"
+            assert agents_only and onehot_nodes, "compact is the single-layer fused path"
+            assert row_gate is None or compact.gate_c is not None
+            egc = compact.gate_c if row_gate is not None else None
+            mp, rm = compact.m_pad, compact.inv  # dW in the dense order: same bits
+            x0 = ops.gather_rows(msg_in.reshape(B * N * D, msg_in.shape[-1]), compact)
+            msg = self.msg_out(self.msg_mlp(x0, egc, mp, rm), egc, mp, rm)  # (cap, msg_dim)
+            msg_a, msg_s = ops.fork_rows(msg, compact)
+            gate = self.attn_out(self.attn_mlp(msg_a, egc, mp, rm), egc, mp, rm).squeeze(-1)
+            aggr = ops.compact_softmax_aggr(gate, msg_s, compact).reshape(B, N, self.msg_dim)
+        else:
+            if msg_in is None:
+                flat_idx = send_idx.reshape(-1)  # (N*D,)
+                sender = node_feats[:, flat_idx].reshape(B, N, D, F)
+                recv = node_feats[:, :N, None, :].expand(B, N, D, F)
+                msg_in = torch.cat([edge_feats, sender, recv], dim=-1)
+            msg = self.msg_out(self.msg_mlp(msg_in, eg), eg)  # (B,N,D,msg_dim)
+            gate = self.attn_out(self.attn_mlp(msg, eg), eg).squeeze(-1)  # (B,N,D)
+            aggr = ops.masked_softmax_aggr(gate, msg, mask)  # (B,N,msg_dim)
         d0 = self.update_mlp.layers[0]
         if agents_only and onehot_nodes and d0.in_dim == 3 + self.msg_dim:
             # agent one-hot is [0,0,1]: cat([onehot, aggr]) @ W ==
@@ -152,7 +171,7 @@ class GNN(nn.Module):
 
     def forward(self, graph: GraphBatch, edge_feats: Optional[Tensor],
                 node_feats: Optional[Tensor] = None, msg_in0: Optional[Tensor] = None,
-                row_gate: Optional[Tensor] = None) -> Tensor:
+                row_gate: Optional[Tensor] = None, compact=None) -> Tensor:
         B = graph.batch_size
         N, R, V = graph.n_agents, graph.n_rays, graph.n_nodes
         n_layers = len(self.layers)
@@ -163,6 +182,9 @@ class GNN(nn.Module):
             # per-row gate cannot express that stop-gradient, so do not lift
             # this for the deep path.
             assert n_layers == 1, "row_gate requires gnn_layers == 1"
+        if compact is not None:
+            assert n_layers == 1 and msg_in0 is not None and node_feats is None, \
+                "compact (ops.EdgeCompact) is for the single-layer fused path"
         if edge_feats is None:
             assert msg_in0 is not None, "edge_feats required unless a fused msg_in0 is given"
             if n_layers >= 2:
@@ -181,7 +203,8 @@ class GNN(nn.Module):
             last = i == n_layers - 1
             x = layer(x, edge_feats, graph.mask, send_idx, agents_only=last,
                       msg_in=msg_in0 if i == 0 else None,
-                      onehot_nodes=onehot and i == 0, row_gate=row_gate)
+                      onehot_nodes=onehot and i == 0, row_gate=row_gate,
+                      compact=compact)
         return x  # (B, N, out_dim)
 
     def _forward_deep(self, graph: GraphBatch, X0: Tensor) -> Tensor:

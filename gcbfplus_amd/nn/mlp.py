@@ -45,8 +45,9 @@ class Dense(nn.Module):
         self.kernel = nn.Parameter(w)
         self.bias = nn.Parameter(torch.zeros(out_dim))
 
-    def forward(self, x: Tensor, row_gate: Optional[Tensor] = None) -> Tensor:
-        return ops.fused_linear(x, self.kernel, self.bias, self.act, row_gate)
+    def forward(self, x: Tensor, row_gate: Optional[Tensor] = None,
+                m_dev: Optional[Tensor] = None, row_map: Optional[Tensor] = None) -> Tensor:
+        return ops.fused_linear(x, self.kernel, self.bias, self.act, row_gate, m_dev, row_map)
 
     def extra_repr(self) -> str:
         return f"in={self.in_dim}, out={self.out_dim}, act={self.act}"
@@ -79,7 +80,8 @@ class MLP(nn.Module):
         self.layers = nn.ModuleList(layers)
         self.out_dim = d
 
-    def forward(self, x: Tensor, row_gate: Optional[Tensor] = None) -> Tensor:
+    def forward(self, x: Tensor, row_gate: Optional[Tensor] = None,
+                m_dev: Optional[Tensor] = None, row_map: Optional[Tensor] = None) -> Tensor:
         for l in self.layers:
-            x = l(x, row_gate)
+            x = l(x, row_gate, m_dev, row_map)
         return x

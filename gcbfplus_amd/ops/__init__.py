@@ -17,6 +17,10 @@ Op inventory (kernel numbering follows SURVEY.md §2.7):
                       run as grouped launches at its exit (GCBF_NO_DEFER_DW=1:
                       immediate launches as outside the scope)
   masked_softmax_aggr K3/K4: per-receiver masked softmax + weighted message sum
+  EdgeCompact         active edge slots of a mask as device index tensors; with
+                      gather_rows / fork_rows / compact_softmax_aggr and the
+                      m_dev row count of fused_linear the edge level of the
+                      GCBF+ minibatch runs on active slots only
   edge_msg_in         K2/K15: fused layer-0 GNN input build (+ analytic bwd);
                       mode 0 state diff, 1 DubinsCar, 2 CrazyFlie (node pre-pass)
   node_msg_in         fused layer >= 1 GNN input (gnn_layers >= 2): edge columns of
@@ -140,7 +144,8 @@ class _FusedLinearHIP(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x: Tensor, w: Tensor, b: Optional[Tensor], act: int,
-                row_gate: Optional[Tensor] = None):
+                row_gate: Optional[Tensor] = None, m_dev: Optional[Tensor] = None,
+                row_map: Optional[Tensor] = None):
         ext = _require_ext()
         x_bf = x if x.dtype == torch.bfloat16 else x.to(torch.bfloat16)
         # FusedAdamW maintains a bf16 shadow per param (p._bf, updated inside
@@ -149,11 +154,19 @@ class _FusedLinearHIP(torch.autograd.Function):
         if w_bf is None:
             w_bf = w.to(torch.bfloat16)
         bias = b if b is not None else _zero_bias(w.shape[1], w.device)
-        y = ext.gemm_bias_act(x_bf.contiguous(), w_bf.contiguous(), bias.contiguous(), act)
+        y = ext.gemm_bias_act(x_bf.contiguous(), w_bf.contiguous(), bias.contiguous(), act,
+                              m_dev)
         ctx.save_for_backward(x_bf, w_bf, y)
         ctx.act = act
         ctx.x_dtype = x.dtype
         ctx.has_bias = b is not None
+        # device row count (edge compaction): every GEMM of this layer, forward
+        # and backward, works on the rows below it only
+        ctx.m_dev = m_dev
+        # dW/db of an edge-compacted layer: summed over the dense slot rows in
+        # the dense call's order (row_map = EdgeCompact.inv), so they keep the
+        # dense path's bits; without it the live rows are summed as they lie
+        ctx.row_map = row_map
         # direct-accumulate target: when w/b are leaf params whose .grad is a
         # live buffer (FusedAdamW flat-gradient views), backward writes dW/db
         # straight into it (+=) and returns None — skips the AccumulateGrad
@@ -191,29 +204,35 @@ class _FusedLinearHIP(torch.autograd.Function):
                 dz = ext.act_bwd(dz, y, actin)  # rare: narrow activated layer
                 actin, yact = ACT_NONE, dz
         dx = dw = db = None
+        md = ctx.m_dev
         if ctx.needs_input_grad[0]:
             if dz.shape[1] % 32 == 0:
                 # dx = dz @ w^T via the transposed B-stage kernel: no
                 # materialized w^T copy per backward
-                dx = ext.gemm_bt(dz, w_bf, yact, actin)
+                dx = ext.gemm_bt(dz, w_bf, yact, actin, md)
             else:
-                # small-N heads: pad path with an explicit transpose
+                # small-N heads: pad path with an explicit transpose (pads K
+                # by a copy, so it runs over every row whatever m_dev says;
+                # rows past the count hold garbage nobody reads)
                 wt = w_bf.t().contiguous()
                 dx = ext.gemm_bias_act(dz, wt, _zero_bias(wt.shape[1], wt.device), ACT_NONE)
             dx = dx.to(ctx.x_dtype)
         if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
             rg = ctx.row_gate
+            rm = ctx.row_map
+            if rm is not None:
+                md = None
             if ctx.acc is not None:
                 wp, bp = ctx.acc
                 if _DEFER_DW:
-                    ext.gemm_tn_defer(x_bf, dz, yact, actin, wp.grad, bp.grad, None, rg)
+                    ext.gemm_tn_defer(x_bf, dz, yact, actin, wp.grad, bp.grad, None, rg, md, rm)
                 else:
-                    ext.gemm_tn_acc(x_bf, dz, yact, actin, wp.grad, bp.grad, rg)
+                    ext.gemm_tn_acc(x_bf, dz, yact, actin, wp.grad, bp.grad, rg, md, rm)
             else:
-                dw, db = ext.gemm_tn(x_bf, dz, yact, actin, rg)  # f32 (K,N), (N,)
+                dw, db = ext.gemm_tn(x_bf, dz, yact, actin, rg, md, rm)  # f32 (K,N), (N,)
         if not ctx.has_bias:
             db = None
-        return dx, dw, db, None, None
+        return dx, dw, db, None, None, None, None
 
 
 class _FusedLinearOneHotHIP(torch.autograd.Function):
@@ -299,12 +318,19 @@ def fused_linear_onehot(x: Tensor, w: Tensor, b: Tensor, act: int, oh: int = 3,
 
 
 def fused_linear(x: Tensor, w: Tensor, b: Optional[Tensor], act: int = ACT_NONE,
-                 row_gate: Optional[Tensor] = None) -> Tensor:
+                 row_gate: Optional[Tensor] = None, m_dev: Optional[Tensor] = None,
+                 row_map: Optional[Tensor] = None) -> Tensor:
     """act(x @ w + b). x: (..., K); w: (K, N) fp32 master weight; b: (N,) fp32.
 
     GPU: bf16 MFMA kernel. CPU: fp32 torch (autograd oracle).
     row_gate (flat rows,) bool: rows with False contribute nothing to dW/db
     (dX unaffected) — per-sample parameter stop-gradient.
+    m_dev: one int32 on the GPU, the live row count of an edge-compacted call
+    (``EdgeCompact.m_pad``): rows at or past it are neither computed nor
+    written, forward or backward, and take no part in dW/db. GPU only.
+    row_map (``EdgeCompact.inv``, with m_dev): dW/db are summed over the dense
+    slot rows in the dense call's order, reading row row_map[m] of the compact
+    operands (zero where it is -1): the dense path's bits.
     """
     lead = x.shape[:-1]
     x2 = x.reshape(-1, x.shape[-1])
@@ -319,9 +345,10 @@ def fused_linear(x: Tensor, w: Tensor, b: Optional[Tensor], act: int = ACT_NONE,
             # slices dW back to the master shape
             w = torch.cat([w, w.new_zeros(x2.shape[-1] - w.shape[0], w.shape[1])], dim=0)
     if x2.is_cuda:
-        y = _FusedLinearHIP.apply(x2, w, b, act, row_gate)
+        y = _FusedLinearHIP.apply(x2, w, b, act, row_gate, m_dev, row_map)
     else:
         assert row_gate is None, "row_gate is a GPU-path feature"
+        assert m_dev is None, "m_dev is a GPU-path feature"
         y = torch.addmm(b, x2, w) if b is not None else x2 @ w
         y = _apply_act(y, act)
     return y.reshape(*lead, w.shape[1])
@@ -372,6 +399,141 @@ def masked_softmax_aggr(gate: Tensor, msg: Tensor, mask: Tensor) -> Tensor:
     denom = e.sum(dim=-1, keepdim=True).clamp_min(1e-20)
     attn = e / denom
     return torch.einsum("bnd,bndc->bnc", attn.to(msg.dtype), msg)
+
+
+# --------------------------------------------------------------------------
+# edge compaction: the edge-level GNN kernels on the active slots only
+# --------------------------------------------------------------------------
+# slot rows up to this take gemm_plan's small-M kernels, where the dense edge
+# level already sits at the launch floor (bindings.hip gemm_plan: M <= 16384)
+EDGE_COMPACT_MIN_ROWS = 16384
+
+
+def edge_compact_wanted(n_slot_rows: int) -> bool:
+    """Shape-only default for the compact edge path (GPU, fused single-layer
+    GNN input): on above the small-M limit. GCBF_NO_EDGE_COMPACT=1 keeps the
+    dense path, GCBF_FORCE_EDGE_COMPACT=1 compacts at any size."""
+    if os.environ.get("GCBF_NO_EDGE_COMPACT"):
+        return False
+    if os.environ.get("GCBF_FORCE_EDGE_COMPACT"):
+        return True
+    return n_slot_rows > EDGE_COMPACT_MIN_ROWS
+
+
+class EdgeCompact:
+    """Active edge slots of a (B, N, D) bool mask as device index tensors
+    (``_C.edge_compact``; nothing is read on the host, so it can be built and
+    used inside a stream capture):
+
+      rows (cap,)   flat slot index of compact row j < count, ascending
+      inv (B*N*D,)  compact row of a slot, -1 if masked
+      off (B*N+1,)  exclusive prefix of the per-receiver active counts
+      cnt (2,)      [count, count rounded up to 128]
+      gate_c (cap,) row_gate[receiver] per compact row (when a gate is given)
+
+    cap = B*N*D rounded up to 128 is the row capacity of every compact tensor.
+    ``m_pad`` (= cnt[1:2]) is the ``m_dev`` of the GEMM family. ``prefix(n)``
+    is the view for the first n receivers: the same rows, because they ascend
+    (GCBF+ runs the actor on g and the CBF on [g; next_g] with one mask)."""
+
+    def __init__(self, rows, inv, off, cnt, gate_c, n_recv: int, D: int):
+        self.rows, self.inv, self.off, self.cnt, self.gate_c = rows, inv, off, cnt, gate_c
+        self.n_recv, self.D = n_recv, D
+        self.n_slots = n_recv * D
+        self.cap = (self.n_slots + 127) // 128 * 128
+        self.m_pad = cnt[1:2]
+        self._prefix = None
+
+    @classmethod
+    def build(cls, mask: Tensor, row_gate: Optional[Tensor] = None,
+              prefix_recv: Optional[int] = None) -> "EdgeCompact":
+        ext = _require_ext()
+        D = mask.shape[-1]
+        n_recv = mask.numel() // D
+        gate = None if row_gate is None else row_gate.reshape(-1).contiguous()
+        out = ext.edge_compact(mask.contiguous(), 128,
+                               n_recv if prefix_recv is None else prefix_recv, gate)
+        rows, inv, off, cnt4 = out[:4]
+        c = cls(rows, inv, off, cnt4[0:2], out[4] if gate is not None else None, n_recv, D)
+        if prefix_recv is not None:
+            c._prefix = cls(rows, inv[: prefix_recv * D], off[: prefix_recv + 1], cnt4[2:4], None,
+                            prefix_recv, D)
+        return c
+
+    def prefix(self) -> "EdgeCompact":
+        assert self._prefix is not None, "built without prefix_recv"
+        return self._prefix
+
+
+class _GatherRowsHIP(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, X: Tensor, ec: EdgeCompact):
+        ext = _require_ext()
+        ctx.ec = ec
+        ctx.M = X.shape[0]
+        return ext.gather_rows(X.contiguous(), ec.rows, ec.cnt, ec.cap)
+
+    @staticmethod
+    def backward(ctx, dXc: Tensor):
+        ext = _require_ext()
+        return ext.gather_rows_bwd(dXc.contiguous(), ctx.ec.inv, ctx.M), None
+
+
+def gather_rows(X: Tensor, ec: EdgeCompact) -> Tensor:
+    """(B*N*D, K) dense slot rows -> (cap, K) compact rows: row j < count is
+    X[rows[j]] bit for bit, rows [count, count_pad) are zeros, later rows are
+    left unwritten. Backward scatters back (zeros in masked slots). GPU only."""
+    assert X.dim() == 2 and X.shape[0] == ec.n_slots
+    return _GatherRowsHIP.apply(X, ec)
+
+
+class _ForkAddHIP(torch.autograd.Function):
+    """x -> (x, x) for a compact bf16 tensor with two consumers: the backward
+    adds the two gradients over the live rows only (``_C.add_rows_bf16``,
+    the rounding of the eager add autograd would run over the whole capacity)."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, ec: EdgeCompact):
+        ctx.ec = ec
+        return x.view_as(x), x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, d1: Tensor, d2: Tensor):
+        ext = _require_ext()
+        return ext.add_rows_bf16(d1.contiguous(), d2.contiguous(), ctx.ec.cnt), None
+
+
+def fork_rows(x: Tensor, ec: EdgeCompact):
+    return _ForkAddHIP.apply(x, ec)
+
+
+class _SoftmaxAggrCompactHIP(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, gate_c: Tensor, msg_c: Tensor, ec: EdgeCompact):
+        ext = _require_ext()
+        aggr, attn_c = ext.softmax_aggr_c_fwd(gate_c.contiguous(), msg_c.contiguous(),
+                                              ec.off, ec.inv, ec.D)
+        ctx.save_for_backward(attn_c, msg_c)
+        ctx.ec = ec
+        return aggr
+
+    @staticmethod
+    def backward(ctx, daggr: Tensor):
+        ext = _require_ext()
+        attn_c, msg_c = ctx.saved_tensors
+        ec = ctx.ec
+        dgate_c, dmsg_c = ext.softmax_aggr_c_bwd(
+            daggr.to(torch.bfloat16).contiguous(), attn_c, msg_c, ec.off, ec.rows, ec.cnt, ec.D)
+        return dgate_c, dmsg_c, None
+
+
+def compact_softmax_aggr(gate_c: Tensor, msg_c: Tensor, ec: EdgeCompact) -> Tensor:
+    """``masked_softmax_aggr`` on compact rows: gate_c (cap,) f32 and msg_c
+    (cap, C) bf16 -> aggr (B*N, C), bit-equal to the dense kernel on the
+    scattered inputs. The backward zeroes the gradients of the padding rows
+    [count, count_pad), which keeps them out of every dW upstream. GPU only."""
+    assert gate_c.dtype == torch.float32 and msg_c.dtype == torch.bfloat16
+    return _SoftmaxAggrCompactHIP.apply(gate_c, msg_c, ec)
 
 
 # --------------------------------------------------------------------------

@@ -14,30 +14,44 @@
 
 // kernel decls (defined in the .hip TUs)
 typedef __bf16 bf16_t_;
+// (the trailing const int* of the GEMM family is m_dev: null, or the device
+// row count of an edge-compacted call, common.h live_rows)
 template <int ACT, bool BT, int ACTIN>
-__global__ void gemm_bias_act_kernel(const bf16_t_*, const bf16_t_*, const float*, bf16_t_*, const bf16_t_*, int, int, int);
+__global__ void gemm_bias_act_kernel(const bf16_t_*, const bf16_t_*, const float*, bf16_t_*, const bf16_t_*, int, int, int, const int*);
 template <int ACT, bool BT, int ACTIN>
-__global__ void gemm_bias_act_sm_kernel(const bf16_t_*, const bf16_t_*, const float*, bf16_t_*, const bf16_t_*, int, int, int);
+__global__ void gemm_bias_act_sm_kernel(const bf16_t_*, const bf16_t_*, const float*, bf16_t_*, const bf16_t_*, int, int, int, const int*);
 template <int ACT, bool BT, int NCH>
-__global__ void gemm_bias_act_panel_kernel(const bf16_t_*, const bf16_t_*, const float*, bf16_t_*, int, int, int, int);
+__global__ void gemm_bias_act_panel_kernel(const bf16_t_*, const bf16_t_*, const float*, bf16_t_*, int, int, int, int, const int*);
 __global__ void reduce_dw_db_kernel(const float*, const float*, float*, float*, float*, long, int, int, int, int, int);
 template <int ACT, typename OutT>
-__global__ void gemv_bias_act_kernel(const bf16_t_*, const bf16_t_*, const float*, OutT*, int, int, int);
+__global__ void gemv_bias_act_kernel(const bf16_t_*, const bf16_t_*, const float*, OutT*, int, int, int, const int*);
 template <int ACT>
-__global__ void dot_bias_act_kernel(const bf16_t_*, const bf16_t_*, const float*, float*, long, int);
+__global__ void dot_bias_act_kernel(const bf16_t_*, const bf16_t_*, const float*, float*, long, int, const int*);
 __global__ void act_bwd_kernel(const bf16_t_*, const bf16_t_*, bf16_t_*, long, int);
 template <int ACT>
-__global__ void gemm_tn_partial_kernel(const bf16_t_*, const bf16_t_*, const bf16_t_*, const bool*, float*, float*, int, int, int, int, int);
+__global__ void gemm_tn_partial_kernel(const bf16_t_*, const bf16_t_*, const bf16_t_*, const bool*, float*, float*, int, int, int, int, int, const int*, const int*, int);
 __global__ void gemm_tn_partial_grouped_kernel(const TnPartialGroup);
 __global__ void reduce_dw_db_grouped_kernel(const DwReduceGroup);
 template <int ACT>
 __global__ void gemm_tn_partial2_kernel(const bf16_t_*, const bf16_t_*, const bf16_t_*, float*, float*, int, int, int, int, int);
 template <int ACT>
-__global__ void gemm_tn_partial3_kernel(const bf16_t_*, const bf16_t_*, const bf16_t_*, const bool*, float*, float*, int, int, int, int, int);
+__global__ void gemm_tn_partial3_kernel(const bf16_t_*, const bf16_t_*, const bf16_t_*, const bool*, float*, float*, int, int, int, int, int, const int*, const int*, int);
 template <int ACT>
 __global__ void gemm_tn_partial4_kernel(const bf16_t_*, const bf16_t_*, const bf16_t_*, float*, float*, int, int, int, int, int);
 __global__ void softmax_aggr_fwd_kernel(const float*, const bf16_t_*, const bool*, bf16_t_*, float*, int, int);
 __global__ void softmax_aggr_bwd_kernel(const bf16_t_*, const float*, const bf16_t_*, float*, bf16_t_*, int, int);
+__global__ void edge_count_kernel(const bool*, int*, int, int);
+__global__ void edge_scan_kernel(const int*, int*, int*, int, int, int);
+__global__ void edge_fill_kernel(const bool*, const int*, const bool*, int*, int*, bool*, int, int);
+__global__ void gather_rows_kernel(const uint4*, const int*, const int*, uint4*, long, long, int);
+__global__ void gather_rows_bwd_kernel(const uint4*, const int*, uint4*, long, long, int);
+typedef __bf16 bf16x8_ __attribute__((ext_vector_type(8)));
+__global__ void add_rows_bf16_kernel(const bf16x8_*, const bf16x8_*, const int*, bf16x8_*, long, int);
+__global__ void softmax_aggr_c_fwd_kernel(const float*, const bf16_t_*, const int*, const int*,
+                                          bf16_t_*, float*, int, int, int);
+__global__ void softmax_aggr_c_bwd_kernel(const bf16_t_*, const float*, const bf16_t_*, const int*,
+                                          const int*, const int*, float*, bf16_t_*, int, int, int,
+                                          int);
 __global__ void raytrace_rect_kernel(const float*, const float*, float*, int, int, int, float);
 __global__ void raytrace_sphere_topk_kernel(const float*, const float*, const float*, float*,
                                             float*, bool*, int, int,
@@ -103,6 +117,17 @@ static inline const bf16_t_* bfp(const torch::Tensor& t) {
 }
 static inline bf16_t_* bfp_mut(torch::Tensor& t) {
   return reinterpret_cast<bf16_t_*>(t.data_ptr<at::BFloat16>());
+}
+
+// Optional device row count of a GEMM-family call (one int32, never read on
+// the host): the kernels take min(*m_dev, M) as their M. Shapes, plans and
+// grids stay those of the static M, so a captured graph replays with any count.
+typedef c10::optional<torch::Tensor> MDev;
+static inline const int* mdev_ptr(const MDev& m_dev) {
+  if (!m_dev) return nullptr;
+  TORCH_CHECK(m_dev->is_cuda() && m_dev->dtype() == torch::kInt32 && m_dev->numel() == 1,
+              "m_dev must be one int32 on the GPU");
+  return m_dev->data_ptr<int>();
 }
 
 // ---------------------------------------------------------------------------
@@ -301,7 +326,7 @@ long gemm_lds_limit_bytes() { return (long)gemm_lds_limit(); }
 template <int ACT, bool BT, int NCH>
 static void launch_panel_nch(const GemmPlan& plan, hipStream_t stream, const bf16_t_* x,
                              const bf16_t_* w, const float* bias, bf16_t_* y, long M, long N,
-                             bool wvec) {
+                             bool wvec, const int* md) {
   static bool opted[64] = {false};  // per device ordinal
   int dev = 0;
   C10_HIP_CHECK(hipGetDevice(&dev));
@@ -313,26 +338,41 @@ static void launch_panel_nch(const GemmPlan& plan, hipStream_t stream, const bf1
     if (slot) opted[dev] = true;
   }
   hipLaunchKernelGGL((gemm_bias_act_panel_kernel<ACT, BT, NCH>), dim3(M / 128), dim3(256),
-                     plan.lds, stream, x, w, bias, y, (int)M, (int)N, plan.wbufs, (int)wvec);
+                     plan.lds, stream, x, w, bias, y, (int)M, (int)N, plan.wbufs, (int)wvec, md);
   C10_HIP_KERNEL_LAUNCH_CHECK();
 }
 
 template <int ACT, bool BT>
 static void launch_panel(const GemmPlan& plan, hipStream_t stream, const bf16_t_* x,
                          const bf16_t_* w, const float* bias, bf16_t_* y, long M, long N, long K,
-                         bool wvec) {
+                         bool wvec, const int* md) {
   switch (K / 64) {
-    case 1: return launch_panel_nch<ACT, BT, 1>(plan, stream, x, w, bias, y, M, N, wvec);
-    case 2: return launch_panel_nch<ACT, BT, 2>(plan, stream, x, w, bias, y, M, N, wvec);
-    case 3: return launch_panel_nch<ACT, BT, 3>(plan, stream, x, w, bias, y, M, N, wvec);
-    case 4: return launch_panel_nch<ACT, BT, 4>(plan, stream, x, w, bias, y, M, N, wvec);
-    case 5: return launch_panel_nch<ACT, BT, 5>(plan, stream, x, w, bias, y, M, N, wvec);
-    case 6: return launch_panel_nch<ACT, BT, 6>(plan, stream, x, w, bias, y, M, N, wvec);
+    case 1: return launch_panel_nch<ACT, BT, 1>(plan, stream, x, w, bias, y, M, N, wvec, md);
+    case 2: return launch_panel_nch<ACT, BT, 2>(plan, stream, x, w, bias, y, M, N, wvec, md);
+    case 3: return launch_panel_nch<ACT, BT, 3>(plan, stream, x, w, bias, y, M, N, wvec, md);
+    case 4: return launch_panel_nch<ACT, BT, 4>(plan, stream, x, w, bias, y, M, N, wvec, md);
+    case 5: return launch_panel_nch<ACT, BT, 5>(plan, stream, x, w, bias, y, M, N, wvec, md);
+    case 6: return launch_panel_nch<ACT, BT, 6>(plan, stream, x, w, bias, y, M, N, wvec, md);
   }
   TORCH_CHECK(false, "row-panel GEMM: no instantiation for K=", K);
 }
 
-torch::Tensor gemm_bias_act(torch::Tensor x, torch::Tensor w, torch::Tensor bias, long act) {
+// the caller's output buffer (tests: shows which rows a call writes), or a
+// fresh one
+static torch::Tensor out_or_empty(const c10::optional<torch::Tensor>& out, long M, long N,
+                                  const torch::TensorOptions& opts) {
+  if (!out) return torch::empty({M, N}, opts);
+  TORCH_CHECK(out->is_cuda() && out->is_contiguous() && out->dim() == 2 && out->size(0) == M &&
+                  out->size(1) == N && out->dtype() == opts.dtype(),
+              "out must be a contiguous (M, N) tensor of the output dtype on the GPU");
+  return *out;
+}
+
+// m_dev: rows >= *m_dev of y are neither computed nor written (the row-panel
+// kernel works in whole 128-row panels: hand it a multiple of 128).
+torch::Tensor gemm_bias_act(torch::Tensor x, torch::Tensor w, torch::Tensor bias, long act,
+                            MDev m_dev = c10::nullopt,
+                            c10::optional<torch::Tensor> out = c10::nullopt) {
   CHECK_IN(x);
   CHECK_IN(w);
   CHECK_IN(bias);
@@ -340,11 +380,13 @@ torch::Tensor gemm_bias_act(torch::Tensor x, torch::Tensor w, torch::Tensor bias
   TORCH_CHECK(bias.dtype() == torch::kFloat32);
   long M = x.size(0), K = x.size(1), N = w.size(1);
   TORCH_CHECK(w.size(0) == K, "K mismatch");
+  const int* md = mdev_ptr(m_dev);
 
   const GemmPlan plan = gemm_plan(GEMM_FWD, M, K, N, 0, false);
   // pad K to a multiple of 32 for the MFMA path (the gather op emits padded
   // inputs on the hot path; this is the generic fallback)
   if (plan.Kp != K) {
+    TORCH_CHECK(md == nullptr && !out, "gemm_bias_act: m_dev / out need K % 32 == 0 (no pad copy)");
     long Kp = plan.Kp;
     auto xp = torch::zeros({M, Kp}, x.options());
     xp.narrow(1, 0, K).copy_(x);
@@ -360,13 +402,13 @@ torch::Tensor gemm_bias_act(torch::Tensor x, torch::Tensor w, torch::Tensor bias
     // small-N head/gate outputs come out in f32: the CBF h enters the
     // h_dot = (h_next - h)/dt finite difference where bf16 storage would
     // cancel catastrophically (bf16 ulp at |h|~1 is 0.008, signal ~0.03h)
-    auto y = torch::empty({M, N}, x.options().dtype(torch::kFloat32));
+    auto y = out_or_empty(out, M, N, x.options().dtype(torch::kFloat32));
     if (M == 0) return y;
     if (plan.kernel == GK_DOT) {  // thread-per-row dot: gate / CBF head
       dim3 grid((M + 255) / 256);
       auto launch = [&](auto kernel) {
         hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, bfp(x), bfp(w),
-                           bias.data_ptr<float>(), y.data_ptr<float>(), M, (int)K);
+                           bias.data_ptr<float>(), y.data_ptr<float>(), M, (int)K, md);
         C10_HIP_KERNEL_LAUNCH_CHECK();
       };
       if (act == 0) launch(dot_bias_act_kernel<0>);
@@ -377,7 +419,7 @@ torch::Tensor gemm_bias_act(torch::Tensor x, torch::Tensor w, torch::Tensor bias
     dim3 grid((M + 3) / 4);
     auto launch = [&](auto kernel) {
       hipLaunchKernelGGL(kernel, grid, dim3(256), smem, stream, bfp(x), bfp(w),
-                         bias.data_ptr<float>(), y.data_ptr<float>(), (int)M, (int)N, (int)K);
+                         bias.data_ptr<float>(), y.data_ptr<float>(), (int)M, (int)N, (int)K, md);
       C10_HIP_KERNEL_LAUNCH_CHECK();
     };
     if (act == 0) launch(gemv_bias_act_kernel<0, float>);
@@ -385,14 +427,14 @@ torch::Tensor gemm_bias_act(torch::Tensor x, torch::Tensor w, torch::Tensor bias
     else launch(gemv_bias_act_kernel<2, float>);
     return y;
   }
-  auto y = torch::empty({M, N}, x.options());
+  auto y = out_or_empty(out, M, N, x.options());
   if (M == 0) return y;
   if (plan.kernel == GK_SM) {
     dim3 grid((M + 31) / 32, (N + 63) / 64);
     auto launch = [&](auto kernel) {
       hipLaunchKernelGGL(kernel, grid, dim3(256), smem, stream, bfp(x), bfp(w),
                          bias.data_ptr<float>(), bfp_mut(y), (const bf16_t_*)nullptr,
-                         (int)M, (int)N, (int)K);
+                         (int)M, (int)N, (int)K, md);
       C10_HIP_KERNEL_LAUNCH_CHECK();
     };
     if (act == 0) launch(gemm_bias_act_sm_kernel<0, false, 0>);
@@ -401,15 +443,15 @@ torch::Tensor gemm_bias_act(torch::Tensor x, torch::Tensor w, torch::Tensor bias
   } else if (plan.kernel == GK_GLDS) {
     // DMA of a W tile needs 16-byte-aligned rows: N % 8 == 0 and an aligned W
     const bool wvec = N % 8 == 0 && ((uintptr_t)w.data_ptr() & 15) == 0;
-    if (act == 0) launch_panel<0, false>(plan, stream, bfp(x), bfp(w), bias.data_ptr<float>(), bfp_mut(y), M, N, K, wvec);
-    else if (act == 1) launch_panel<1, false>(plan, stream, bfp(x), bfp(w), bias.data_ptr<float>(), bfp_mut(y), M, N, K, wvec);
-    else launch_panel<2, false>(plan, stream, bfp(x), bfp(w), bias.data_ptr<float>(), bfp_mut(y), M, N, K, wvec);
+    if (act == 0) launch_panel<0, false>(plan, stream, bfp(x), bfp(w), bias.data_ptr<float>(), bfp_mut(y), M, N, K, wvec, md);
+    else if (act == 1) launch_panel<1, false>(plan, stream, bfp(x), bfp(w), bias.data_ptr<float>(), bfp_mut(y), M, N, K, wvec, md);
+    else launch_panel<2, false>(plan, stream, bfp(x), bfp(w), bias.data_ptr<float>(), bfp_mut(y), M, N, K, wvec, md);
   } else {
     dim3 grid((M + 127) / 128, (N + 63) / 64);
     auto launch = [&](auto kernel) {
       hipLaunchKernelGGL(kernel, grid, dim3(256), smem, stream, bfp(x), bfp(w),
                          bias.data_ptr<float>(), bfp_mut(y), (const bf16_t_*)nullptr,
-                         (int)M, (int)N, (int)K);
+                         (int)M, (int)N, (int)K, md);
       C10_HIP_KERNEL_LAUNCH_CHECK();
     };
     if (act == 0) launch(gemm_bias_act_kernel<0, false, 0>);
@@ -482,24 +524,43 @@ struct TnCall {
   torch::Tensor partial, db_partial;  // (S, K, N), (S, N) f32
   const bf16_t_* ya;
   const bool* rg;
+  const int* md;  // device row count, or null
+  const int* rmap;  // dense slot row -> row of x / dz (tn_map_row), or null
+  int xrows;
 };
 
 static TnCall tn_prepare(const torch::Tensor& x, const torch::Tensor& dz,
                          const torch::Tensor& yact, long actin,
-                         const c10::optional<torch::Tensor>& rowgate) {
+                         const c10::optional<torch::Tensor>& rowgate,
+                         const MDev& m_dev = c10::nullopt, const MDev& row_map = c10::nullopt) {
   CHECK_IN(x);
   CHECK_IN(dz);
   TnCall c;
   c.M = x.size(0), c.K = x.size(1), c.N = dz.size(1);
   TORCH_CHECK(dz.size(0) == c.M);
+  const long xrows = c.M;
+  c.rmap = nullptr;
+  c.xrows = (int)xrows;
+  if (row_map) {
+    // M, the plan and the slabs are those of the dense rows the map covers
+    TORCH_CHECK(row_map->is_cuda() && row_map->is_contiguous() &&
+                    row_map->dtype() == torch::kInt32 && row_map->numel() >= 1 && !m_dev,
+                "row_map must be contiguous int32 on the GPU, without m_dev");
+    c.rmap = row_map->data_ptr<int>();
+    c.M = row_map->numel();
+  }
   c.plan = gemm_plan(GEMM_TN, c.M, c.K, c.N, actin, rowgate.has_value());
+  c.md = mdev_ptr(m_dev);
+  TORCH_CHECK((c.md == nullptr && c.rmap == nullptr) || c.plan.kernel == GK_TN1 ||
+                  c.plan.kernel == GK_TN3,
+              "dW with m_dev / row_map: only the tn1 and tn3 kernels take them");
   auto opts = x.options().dtype(torch::kFloat32);
   c.partial = torch::empty({c.plan.S, c.K, c.N}, opts);
   c.db_partial = torch::empty({c.plan.S, c.N}, opts);
   c.ya = actin ? bfp(yact) : nullptr;
   c.rg = nullptr;
   if (rowgate) {
-    TORCH_CHECK(rowgate->is_contiguous() && rowgate->numel() == c.M
+    TORCH_CHECK(rowgate->is_contiguous() && rowgate->numel() == xrows
                 && rowgate->dtype() == torch::kBool);
     c.rg = rowgate->data_ptr<bool>();
   }
@@ -518,7 +579,7 @@ static void tn_launch_partial(TnCall& c, const torch::Tensor& x, const torch::Te
     hipLaunchKernelGGL(kernel, remap ? dim3(gk * gn * S) : dim3(gk, gn, S), dim3(256), 0,
                        stream, bfp(x), bfp(dz), ya, rg, c.partial.data_ptr<float>(),
                        c.db_partial.data_ptr<float>(), (int)M, (int)N, (int)K, (int)S,
-                       remap ? 1 : 0);
+                       remap ? 1 : 0, c.md, c.rmap, c.xrows);
     C10_HIP_KERNEL_LAUNCH_CHECK();
   };
   auto launch24 = [&](auto kernel) {  // kernels 2/4: no rowgate param
@@ -551,8 +612,10 @@ std::vector<torch::Tensor> gemm_tn_impl(torch::Tensor x, torch::Tensor dz,
                                         torch::Tensor yact, long actin,
                                         torch::Tensor dw, torch::Tensor db, bool acc,
                                         c10::optional<torch::Tensor> db2 = c10::nullopt,
-                                        c10::optional<torch::Tensor> rowgate = c10::nullopt) {
-  TnCall c = tn_prepare(x, dz, yact, actin, rowgate);
+                                        c10::optional<torch::Tensor> rowgate = c10::nullopt,
+                                        MDev m_dev = c10::nullopt,
+                                        MDev row_map = c10::nullopt) {
+  TnCall c = tn_prepare(x, dz, yact, actin, rowgate, m_dev, row_map);
   auto stream = cur_stream();
   tn_launch_partial(c, x, dz, actin, stream);
   launch_reduce_dw_db(c.partial.data_ptr<float>(), c.db_partial.data_ptr<float>(),
@@ -563,30 +626,33 @@ std::vector<torch::Tensor> gemm_tn_impl(torch::Tensor x, torch::Tensor dz,
 
 std::vector<torch::Tensor> gemm_tn(torch::Tensor x, torch::Tensor dz, torch::Tensor yact,
                                    long actin,
-                                   c10::optional<torch::Tensor> rowgate = c10::nullopt) {
+                                   c10::optional<torch::Tensor> rowgate = c10::nullopt,
+                                   MDev m_dev = c10::nullopt, MDev row_map = c10::nullopt) {
   auto opts = x.options().dtype(torch::kFloat32);
   auto dw = torch::empty({x.size(1), dz.size(1)}, opts);
   auto db = torch::empty({dz.size(1)}, opts);
-  return gemm_tn_impl(x, dz, yact, actin, dw, db, false, c10::nullopt, rowgate);
+  return gemm_tn_impl(x, dz, yact, actin, dw, db, false, c10::nullopt, rowgate, m_dev, row_map);
 }
 
 void gemm_tn_acc(torch::Tensor x, torch::Tensor dz, torch::Tensor yact, long actin,
                  torch::Tensor dw, torch::Tensor db,
-                 c10::optional<torch::Tensor> rowgate = c10::nullopt) {
+                 c10::optional<torch::Tensor> rowgate = c10::nullopt,
+                 MDev m_dev = c10::nullopt, MDev row_map = c10::nullopt) {
   TORCH_CHECK(dw.is_cuda() && dw.is_contiguous() && db.is_contiguous());
   TORCH_CHECK(dw.size(0) == x.size(1) && dw.size(1) == dz.size(1) && db.size(0) == dz.size(1));
-  gemm_tn_impl(x, dz, yact, actin, dw, db, true, c10::nullopt, rowgate);
+  gemm_tn_impl(x, dz, yact, actin, dw, db, true, c10::nullopt, rowgate, m_dev, row_map);
 }
 
 // one-hot fold backward: dw += X^T dZ into a kernel.grad row-slice, db +=
 // into BOTH bias.grad and kernel.grad[oh_row] in the same reduction pass
 void gemm_tn_acc2(torch::Tensor x, torch::Tensor dz, torch::Tensor yact, long actin,
                   torch::Tensor dw, torch::Tensor db, torch::Tensor db2,
-                  c10::optional<torch::Tensor> rowgate = c10::nullopt) {
+                  c10::optional<torch::Tensor> rowgate = c10::nullopt,
+                  MDev m_dev = c10::nullopt, MDev row_map = c10::nullopt) {
   TORCH_CHECK(dw.is_cuda() && dw.is_contiguous() && db.is_contiguous() && db2.is_contiguous());
   TORCH_CHECK(dw.size(0) == x.size(1) && dw.size(1) == dz.size(1) && db.size(0) == dz.size(1));
   TORCH_CHECK(db2.numel() == db.numel());
-  gemm_tn_impl(x, dz, yact, actin, dw, db, true, db2, rowgate);
+  gemm_tn_impl(x, dz, yact, actin, dw, db, true, db2, rowgate, m_dev, row_map);
 }
 
 // ---------------------------------------------------------------------------
@@ -693,7 +759,8 @@ void dw_discard() {
 void gemm_tn_defer(torch::Tensor x, torch::Tensor dz, torch::Tensor yact, long actin,
                    torch::Tensor dw, torch::Tensor db,
                    c10::optional<torch::Tensor> db2 = c10::nullopt,
-                   c10::optional<torch::Tensor> rowgate = c10::nullopt) {
+                   c10::optional<torch::Tensor> rowgate = c10::nullopt,
+                   MDev m_dev = c10::nullopt, MDev row_map = c10::nullopt) {
   auto f32 = [](const torch::Tensor& t) {
     return t.is_cuda() && t.is_contiguous() && t.dtype() == torch::kFloat32;
   };
@@ -707,9 +774,12 @@ void gemm_tn_defer(torch::Tensor x, torch::Tensor dz, torch::Tensor yact, long a
     CHECK_IN(yact);
     TORCH_CHECK(yact.dtype() == torch::kBFloat16 && yact.numel() == dz.numel());
   }
-  TnCall c = tn_prepare(x, dz, yact, actin, rowgate);
+  TnCall c = tn_prepare(x, dz, yact, actin, rowgate, m_dev, row_map);
   const GemmPlan& plan = c.plan;
   const hipStream_t stream = cur_stream();
+  // a call with a device row count is edge-level: it runs at once, the
+  // grouped kernels stay without one
+  const bool defer = plan.defer && c.md == nullptr && c.rmap == nullptr;
 
   DwEntry e;
   e.ndst = 0;
@@ -735,7 +805,7 @@ void gemm_tn_defer(torch::Tensor x, torch::Tensor dz, torch::Tensor yact, long a
           overlap |= o.dst_lo[i] < e.dst_hi[j] && e.dst_lo[j] < o.dst_hi[i];
     if (overlap) dw_flush_locked();
   }
-  if (!plan.defer) {
+  if (!defer) {
     tn_launch_partial(c, x, dz, actin, stream);
     launch_reduce_dw_db(c.partial.data_ptr<float>(), c.db_partial.data_ptr<float>(),
                         dw.data_ptr<float>(), db.data_ptr<float>(),
@@ -763,14 +833,17 @@ void gemm_tn_defer(torch::Tensor x, torch::Tensor dz, torch::Tensor yact, long a
 // dX = dZ @ W^T with W the original forward weight (N, K): no transpose
 // copy. actin != 0 folds dZ = dY * act'(Y) into the A-operand stage (dz is
 // then dY and yact the saved activation) — kills the act_bwd pass.
-torch::Tensor gemm_bt(torch::Tensor dz, torch::Tensor w, torch::Tensor yact, long actin) {
+torch::Tensor gemm_bt(torch::Tensor dz, torch::Tensor w, torch::Tensor yact, long actin,
+                      MDev m_dev = c10::nullopt,
+                      c10::optional<torch::Tensor> out = c10::nullopt) {
   CHECK_IN(dz);
   CHECK_IN(w);
+  const int* md = mdev_ptr(m_dev);
   TORCH_CHECK(dz.dtype() == torch::kBFloat16 && w.dtype() == torch::kBFloat16);
   long M = dz.size(0), K = dz.size(1), N = w.size(0);
   TORCH_CHECK(w.size(1) == K, "W cols must equal dZ cols");
   TORCH_CHECK(K % 32 == 0, "BT path needs reduction dim % 32 == 0");
-  auto y = torch::empty({M, N}, dz.options());
+  auto y = out_or_empty(out, M, N, dz.options());
   auto stream = cur_stream();
   static torch::Tensor zb;  // zero bias cache (per device lifetime)
   if (!zb.defined() || zb.numel() < N || zb.device() != dz.device())
@@ -785,7 +858,7 @@ torch::Tensor gemm_bt(torch::Tensor dz, torch::Tensor w, torch::Tensor yact, lon
     dim3 grid((M + 31) / 32, (N + 63) / 64);
     auto launch = [&](auto kernel) {
       hipLaunchKernelGGL(kernel, grid, dim3(256), smem, stream, bfp(dz), bfp(w), bias,
-                         bfp_mut(y), ya, (int)M, (int)N, (int)K);
+                         bfp_mut(y), ya, (int)M, (int)N, (int)K, md);
       C10_HIP_KERNEL_LAUNCH_CHECK();
     };
     if (actin == 1) launch(gemm_bias_act_sm_kernel<0, true, 1>);
@@ -793,12 +866,12 @@ torch::Tensor gemm_bt(torch::Tensor dz, torch::Tensor w, torch::Tensor yact, lon
     else launch(gemm_bias_act_sm_kernel<0, true, 0>);
   } else if (plan.kernel == GK_GLDS) {
     const bool wvec = ((uintptr_t)w.data_ptr() & 15) == 0;  // rows: K % 64 == 0
-    launch_panel<0, true>(plan, stream, bfp(dz), bfp(w), bias, bfp_mut(y), M, N, K, wvec);
+    launch_panel<0, true>(plan, stream, bfp(dz), bfp(w), bias, bfp_mut(y), M, N, K, wvec, md);
   } else {
     dim3 grid((M + 127) / 128, (N + 63) / 64);
     auto launch = [&](auto kernel) {
       hipLaunchKernelGGL(kernel, grid, dim3(256), smem, stream, bfp(dz), bfp(w), bias,
-                         bfp_mut(y), ya, (int)M, (int)N, (int)K);
+                         bfp_mut(y), ya, (int)M, (int)N, (int)K, md);
       C10_HIP_KERNEL_LAUNCH_CHECK();
     };
     if (actin == 1) launch(gemm_bias_act_kernel<0, true, 1>);
@@ -867,6 +940,165 @@ std::vector<torch::Tensor> softmax_aggr_bwd(torch::Tensor daggr, torch::Tensor a
                      bfp(daggr), attn.data_ptr<float>(), bfp(msg), dgate.data_ptr<float>(),
                      bfp_mut(dmsg), D, C);
   return {dgate, dmsg};
+}
+
+// ---------------------------------------------------------------------------
+// Edge compaction (edge_compact.hip). Everything is capturable: no count is
+// read on the host, outputs have the static capacity.
+// ---------------------------------------------------------------------------
+static inline const int* i32p(const torch::Tensor& t, const char* name, long min_numel) {
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.dtype() == torch::kInt32 &&
+                  t.numel() >= min_numel,
+              name, " must be contiguous int32 on the GPU with at least ", min_numel, " elements");
+  return t.data_ptr<int>();
+}
+
+// mask (..., D) bool, receivers R = numel / D -> {rows (cap,), inv (R*D,),
+// off (R+1,), cnt (4,) [, gate_c (cap,) bool = gate[receiver of the row]]}:
+// cnt = {count, ceil_align(count), count of the first prefix_recv receivers,
+// its ceil_align}; cap = ceil_align(R*D). rows[j >= count] is unspecified.
+std::vector<torch::Tensor> edge_compact(torch::Tensor mask, long align, long prefix_recv,
+                                        c10::optional<torch::Tensor> gate) {
+  CHECK_IN(mask);
+  TORCH_CHECK(mask.dtype() == torch::kBool && mask.dim() >= 1 && mask.numel() > 0);
+  TORCH_CHECK(align >= 1 && align <= 65536);
+  const long D = mask.size(-1), M = mask.numel(), R = M / D;
+  const long cap = (M + align - 1) / align * align;
+  TORCH_CHECK(cap <= INT_MAX, "edge_compact: too many slots");
+  if (prefix_recv < 0) prefix_recv = R;
+  TORCH_CHECK(prefix_recv <= R, "edge_compact: prefix_recv past the receivers");
+  const bool* gp = nullptr;
+  if (gate) {
+    TORCH_CHECK(gate->is_cuda() && gate->is_contiguous() && gate->dtype() == torch::kBool &&
+                    gate->numel() == R,
+                "edge_compact: gate must be one bool per receiver");
+    gp = gate->data_ptr<bool>();
+  }
+  auto iopts = mask.options().dtype(torch::kInt32);
+  auto rows = torch::empty({cap}, iopts);
+  auto inv = torch::empty({M}, iopts);
+  auto off = torch::empty({R + 1}, iopts);
+  auto cnt = torch::empty({4}, iopts);
+  auto cnt_r = torch::empty({R}, iopts);
+  torch::Tensor gate_c;
+  if (gate) gate_c = torch::empty({cap}, mask.options());
+  auto stream = cur_stream();
+  const dim3 grid((R + 3) / 4);
+  hipLaunchKernelGGL(edge_count_kernel, grid, dim3(256), 0, stream, mask.data_ptr<bool>(),
+                     cnt_r.data_ptr<int>(), (int)R, (int)D);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  hipLaunchKernelGGL(edge_scan_kernel, dim3(1), dim3(1024), 0, stream, cnt_r.data_ptr<int>(),
+                     off.data_ptr<int>(), cnt.data_ptr<int>(), (int)R, (int)prefix_recv,
+                     (int)align);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  hipLaunchKernelGGL(edge_fill_kernel, grid, dim3(256), 0, stream, mask.data_ptr<bool>(),
+                     off.data_ptr<int>(), gp, rows.data_ptr<int>(), inv.data_ptr<int>(),
+                     gate ? gate_c.data_ptr<bool>() : nullptr, (int)R, (int)D);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  if (gate) return {rows, inv, off, cnt, gate_c};
+  return {rows, inv, off, cnt};
+}
+
+static int row_chunks16(const torch::Tensor& t, const char* who) {
+  const long bytes = t.size(1) * (long)t.element_size();
+  TORCH_CHECK(t.dim() == 2 && bytes % 16 == 0 && ((uintptr_t)t.data_ptr() & 15) == 0, who,
+              ": rows must be whole 16-byte pieces of an aligned 2-D tensor");
+  return (int)(bytes / 16);
+}
+
+// Xc (cap, K): X[rows[j]] for j < cnt[0], zeros up to cnt[1], untouched past it
+torch::Tensor gather_rows(torch::Tensor X, torch::Tensor rows, torch::Tensor cnt, long cap) {
+  CHECK_IN(X);
+  const int chunks = row_chunks16(X, "gather_rows");
+  TORCH_CHECK(cap >= 1 && cap % 8 == 0);
+  const int* rp = i32p(rows, "rows", cap);
+  const int* cp = i32p(cnt, "cnt", 2);
+  auto Xc = torch::empty({cap, X.size(1)}, X.options());
+  const long total = cap * chunks;
+  hipLaunchKernelGGL(gather_rows_kernel, dim3((total + 255) / 256), dim3(256), 0, cur_stream(),
+                     (const uint4*)X.data_ptr(), rp, cp, (uint4*)Xc.data_ptr(), X.size(0), cap,
+                     chunks);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return Xc;
+}
+
+// dX (M, K): dXc[inv[m]], or zeros where inv[m] < 0
+torch::Tensor gather_rows_bwd(torch::Tensor dXc, torch::Tensor inv, long M) {
+  CHECK_IN(dXc);
+  const int chunks = row_chunks16(dXc, "gather_rows_bwd");
+  const int* ip = i32p(inv, "inv", M);
+  auto dX = torch::empty({M, dXc.size(1)}, dXc.options());
+  const long total = M * chunks;
+  if (total == 0) return dX;
+  hipLaunchKernelGGL(gather_rows_bwd_kernel, dim3((total + 255) / 256), dim3(256), 0,
+                     cur_stream(), (const uint4*)dXc.data_ptr(), ip, (uint4*)dX.data_ptr(), M,
+                     dXc.size(0), chunks);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return dX;
+}
+
+// a + b (bf16, f32 add, one rounding) over rows < cnt[1]; other rows untouched
+torch::Tensor add_rows_bf16(torch::Tensor a, torch::Tensor b, torch::Tensor cnt) {
+  CHECK_IN(a);
+  CHECK_IN(b);
+  TORCH_CHECK(a.dtype() == torch::kBFloat16 && b.dtype() == torch::kBFloat16 &&
+              a.sizes() == b.sizes());
+  const int chunks = row_chunks16(a, "add_rows_bf16");
+  row_chunks16(b, "add_rows_bf16");
+  const int* cp = i32p(cnt, "cnt", 2);
+  auto out = torch::empty_like(a);
+  const long cap = a.size(0), total = cap * chunks;
+  if (total == 0) return out;
+  hipLaunchKernelGGL(add_rows_bf16_kernel, dim3((total + 255) / 256), dim3(256), 0, cur_stream(),
+                     (const bf16x8_*)a.data_ptr(), (const bf16x8_*)b.data_ptr(), cp,
+                     (bf16x8_*)out.data_ptr(), cap, chunks);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return out;
+}
+
+// compact gate_c (cap,) f32, msg_c (cap, C) bf16 -> aggr (R, C) bf16, attn_c (cap,) f32
+std::vector<torch::Tensor> softmax_aggr_c_fwd(torch::Tensor gate_c, torch::Tensor msg_c,
+                                              torch::Tensor off, torch::Tensor inv, long D) {
+  CHECK_IN(gate_c);
+  CHECK_IN(msg_c);
+  TORCH_CHECK(gate_c.dtype() == torch::kFloat32 && msg_c.dtype() == torch::kBFloat16);
+  TORCH_CHECK(msg_c.dim() == 2 && gate_c.numel() == msg_c.size(0));
+  const long R = off.numel() - 1, C = msg_c.size(1);
+  TORCH_CHECK(R >= 1 && D >= 1 && R * D <= msg_c.size(0), "softmax_aggr_c_fwd: capacity");
+  const int* op = i32p(off, "off", R + 1);
+  const int* ip = i32p(inv, "inv", R * D);
+  auto aggr = torch::empty({R, C}, msg_c.options());
+  auto attn_c = torch::empty_like(gate_c);
+  hipLaunchKernelGGL(softmax_aggr_c_fwd_kernel, dim3(R), dim3(256), 2 * D * sizeof(float),
+                     cur_stream(), gate_c.data_ptr<float>(), bfp(msg_c), op, ip, bfp_mut(aggr),
+                     attn_c.data_ptr<float>(), (int)D, (int)C, (int)msg_c.size(0));
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return {aggr, attn_c};
+}
+
+// -> dgate_c (cap,) f32, dmsg_c (cap, C) bf16; rows [cnt[0], cnt[1]) zeroed
+std::vector<torch::Tensor> softmax_aggr_c_bwd(torch::Tensor daggr, torch::Tensor attn_c,
+                                              torch::Tensor msg_c, torch::Tensor off,
+                                              torch::Tensor rows, torch::Tensor cnt, long D) {
+  CHECK_IN(daggr);
+  CHECK_IN(attn_c);
+  CHECK_IN(msg_c);
+  TORCH_CHECK(daggr.dtype() == torch::kBFloat16 && attn_c.dtype() == torch::kFloat32 &&
+              msg_c.dtype() == torch::kBFloat16);
+  const long R = off.numel() - 1, C = msg_c.size(1), cap = msg_c.size(0);
+  TORCH_CHECK(R >= 1 && D >= 1 && R * D <= cap && attn_c.numel() == cap &&
+                  daggr.numel() == R * C,
+              "softmax_aggr_c_bwd: shapes");
+  const int* op = i32p(off, "off", R + 1);
+  const int* rp = i32p(rows, "rows", R * D);
+  const int* cp = i32p(cnt, "cnt", 2);
+  auto dgate_c = torch::empty_like(attn_c);
+  auto dmsg_c = torch::empty_like(msg_c);
+  hipLaunchKernelGGL(softmax_aggr_c_bwd_kernel, dim3(R + 1), dim3(256), 3 * D * sizeof(float),
+                     cur_stream(), bfp(daggr), attn_c.data_ptr<float>(), bfp(msg_c), op, rp, cp,
+                     dgate_c.data_ptr<float>(), bfp_mut(dmsg_c), (int)R, (int)D, (int)C, (int)cap);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return {dgate_c, dmsg_c};
 }
 
 torch::Tensor raytrace_rect(torch::Tensor pos, torch::Tensor points, long n_rays, double range) {
@@ -1521,7 +1753,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("dw"), py::arg("db"), py::arg("db2") = py::none(), py::arg("acc") = false);
   m.def("gemm_tn_acc2", &gemm_tn_acc2, py::arg("x"), py::arg("dz"), py::arg("yact"),
         py::arg("actin"), py::arg("dw"), py::arg("db"), py::arg("db2"),
-        py::arg("rowgate") = py::none());
+        py::arg("rowgate") = py::none(), py::arg("m_dev") = py::none(), py::arg("row_map") = py::none());
   m.def("gcbf_loss_fwd", &gcbf_loss_fwd);
   m.def("gcbf_loss_bwd", &gcbf_loss_bwd);
   m.def("edge_msg_in_fwd", &edge_msg_in_fwd);
@@ -1539,7 +1771,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("proxqp_solve", &proxqp_solve_hip, "batched dense QP, one wave per problem (K11)");
   m.def("proxqp_path", &proxqp_path,
         "proxqp_kernel instantiation for (nv, k): w32x16 | w64x32 | none (torch path)");
-  m.def("gemm_bias_act", &gemm_bias_act, "Y = act(X@W + b), MFMA bf16");
+  m.def("gemm_bias_act", &gemm_bias_act, "Y = act(X@W + b), MFMA bf16", py::arg("x"),
+        py::arg("w"), py::arg("bias"), py::arg("act"), py::arg("m_dev") = py::none(),
+        py::arg("out") = py::none());
   m.def("gemm_path", &gemm_path, "kernel a GEMM-family op selects for a shape (no launch)",
         py::arg("op"), py::arg("M"), py::arg("K"), py::arg("N"), py::arg("actin") = 0,
         py::arg("gated") = false);
@@ -1548,17 +1782,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_lds_limit", &gemm_lds_limit_bytes,
         "dynamic LDS bytes a workgroup may request on the current device");
   m.def("act_bwd", &act_bwd, "dZ = dY * act'(Y)");
-  m.def("gemm_bt", &gemm_bt, "dX = dZ @ W^T (transposed B-stage, no copy)");
+  m.def("gemm_bt", &gemm_bt, "dX = dZ @ W^T (transposed B-stage, no copy)", py::arg("dz"),
+        py::arg("w"), py::arg("yact"), py::arg("actin"), py::arg("m_dev") = py::none(),
+        py::arg("out") = py::none());
   m.def("gemm_tn", &gemm_tn, "dW = X^T dZ, db = colsum dZ (deterministic)",
         py::arg("x"), py::arg("dz"), py::arg("yact"), py::arg("actin"),
-        py::arg("rowgate") = py::none());
+        py::arg("rowgate") = py::none(), py::arg("m_dev") = py::none(), py::arg("row_map") = py::none());
   m.def("gemm_tn_acc", &gemm_tn_acc, py::arg("x"), py::arg("dz"), py::arg("yact"),
         py::arg("actin"), py::arg("dw"), py::arg("db"),
-        py::arg("rowgate") = py::none());
+        py::arg("rowgate") = py::none(), py::arg("m_dev") = py::none(), py::arg("row_map") = py::none());
   m.def("gemm_tn_defer", &gemm_tn_defer,
         "gemm_tn_acc / gemm_tn_acc2 with the small-M launches queued for dw_flush",
         py::arg("x"), py::arg("dz"), py::arg("yact"), py::arg("actin"), py::arg("dw"),
-        py::arg("db"), py::arg("db2") = py::none(), py::arg("rowgate") = py::none());
+        py::arg("db"), py::arg("db2") = py::none(), py::arg("rowgate") = py::none(),
+        py::arg("m_dev") = py::none(), py::arg("row_map") = py::none());
   m.def("dw_flush", &dw_flush, "run the deferred dW queue as grouped launches");
   m.def("dw_pending", &dw_pending, "entries in the deferred dW queue");
   m.def("dw_discard", &dw_discard, "drop the deferred dW queue without running it");
@@ -1566,6 +1803,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "(grouped partial, grouped reduce) launches issued by this process so far");
   m.def("softmax_aggr_fwd", &softmax_aggr_fwd);
   m.def("softmax_aggr_bwd", &softmax_aggr_bwd);
+  m.def("edge_compact", &edge_compact,
+        "bool mask (..., D) -> [rows, inv, off, cnt(, gate_c)]: active slots in ascending order",
+        py::arg("mask"), py::arg("align") = 128, py::arg("prefix_recv") = -1,
+        py::arg("gate") = py::none());
+  m.def("gather_rows", &gather_rows, "compact rows of X: X[rows[j]], zero padding rows",
+        py::arg("X"), py::arg("rows"), py::arg("cnt"), py::arg("cap"));
+  m.def("gather_rows_bwd", &gather_rows_bwd, "dense gradient of gather_rows",
+        py::arg("dXc"), py::arg("inv"), py::arg("M"));
+  m.def("add_rows_bf16", &add_rows_bf16, "a + b over the live compact rows",
+        py::arg("a"), py::arg("b"), py::arg("cnt"));
+  m.def("softmax_aggr_c_fwd", &softmax_aggr_c_fwd, py::arg("gate_c"), py::arg("msg_c"),
+        py::arg("off"), py::arg("inv"), py::arg("D"));
+  m.def("softmax_aggr_c_bwd", &softmax_aggr_c_bwd, py::arg("daggr"), py::arg("attn_c"),
+        py::arg("msg_c"), py::arg("off"), py::arg("rows"), py::arg("cnt"), py::arg("D"));
   m.def("mb_gather", &mb_gather, "fused 5-tensor minibatch gather (K18)");
   m.def("raytrace_rect", &raytrace_rect);
   m.def("raytrace_sphere_topk", &raytrace_sphere_topk);

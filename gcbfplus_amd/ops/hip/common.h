@@ -31,6 +31,15 @@ __device__ __forceinline__ float act_grad_from_out(float y, int act) {
   return 1.f;
 }
 
+// Live row count of a call whose buffers keep a static worst-case M (edge
+// compaction under a captured graph): m_dev is null or one int32 in device
+// memory, read once per workgroup as a uniform load.
+__device__ __forceinline__ int live_rows(const int* __restrict__ m_dev, int M) {
+  if (m_dev == nullptr) return M;
+  const int m = *m_dev;
+  return m < M ? m : M;
+}
+
 __device__ __forceinline__ float wave_reduce_sum(float v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, WAVE);

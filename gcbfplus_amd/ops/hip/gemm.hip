@@ -23,6 +23,14 @@
 //   ..._grouped_kernel        : the small-M (tn1) partial and the reduce for
 //                               up to 16 independent problems per launch
 //                               (deferred dW: gemm_tn_defer / dw_flush).
+// Device row count: dot, gemv, sm, the 128x64 kernel, the row panel, tn1 and
+// tn3 take a last argument m_dev (null, or one int32 in device memory) and
+// work on min(*m_dev, M) rows: workgroups past it leave at entry, the dW
+// kernels spread the live rows over their S slabs. Grids and plans stay those
+// of the static M, so edge-compacted calls replay from a captured graph with
+// any count (edge_compact.hip). With m_dev null nothing changes. Training
+// gives tn1 / tn3 a row map instead (tn_map_row): the dense call's summation
+// order over compact operands, so dW/db keep the dense call's bits.
 #include "common.h"
 #include "dw_group.h"
 
@@ -84,7 +92,8 @@ template <int ACT, bool BT, int ACTIN>
 __launch_bounds__(256) __global__
 void gemm_bias_act_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ W,
                           const float* __restrict__ bias, bf16_t* __restrict__ Y,
-                          const bf16_t* __restrict__ Xact, int M, int N, int K) {
+                          const bf16_t* __restrict__ Xact, int M, int N, int K,
+                          const int* __restrict__ m_dev) {
   constexpr int BM = 128, BN = 64, BK = 32, APAD = 40;
   extern __shared__ char smem[];
   bf16_t* sB = (bf16_t*)smem;                    // [K/8][BN][8]
@@ -96,6 +105,8 @@ void gemm_bias_act_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict
   const int wm = w >> 1, wn = w & 1;  // wave tile: 64(M) x 32(N)
   const int m0 = blockIdx.x * BM;
   const int n0 = blockIdx.y * BN;
+  M = live_rows(m_dev, M);
+  if (m0 >= M) return;  // block-uniform, ahead of every barrier and LDS write
 
   // ---- preload W block n0..n0+63 into k-blocked LDS image ----------------
   // chunk c -> k = c>>3, col8 = (c&7)*8 ; threads cover K*8 chunks.
@@ -176,7 +187,8 @@ template <int ACT, bool BT, int ACTIN>
 __launch_bounds__(256) __global__
 void gemm_bias_act_sm_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ W,
                              const float* __restrict__ bias, bf16_t* __restrict__ Y,
-                             const bf16_t* __restrict__ Xact, int M, int N, int K) {
+                             const bf16_t* __restrict__ Xact, int M, int N, int K,
+                             const int* __restrict__ m_dev) {
   constexpr int BM = 32, BN = 64, BK = 32, APAD = 40;
   extern __shared__ char smem[];
   bf16_t* sB = (bf16_t*)smem;                                        // [K/8][BN][8]
@@ -188,6 +200,8 @@ void gemm_bias_act_sm_kernel(const bf16_t* __restrict__ X, const bf16_t* __restr
   const int wm = w >> 1, wn = w & 1;  // wave tile: 16(M) x 32(N)
   const int m0 = blockIdx.x * BM;
   const int n0 = blockIdx.y * BN;
+  M = live_rows(m_dev, M);
+  if (m0 >= M) return;  // block-uniform, ahead of every barrier and LDS write
 
   stage_B_image<BT>(W, sB, N, K, n0, tid);
 
@@ -240,12 +254,12 @@ void gemm_bias_act_sm_kernel(const bf16_t* __restrict__ X, const bf16_t* __restr
   }
 }
 
-template __global__ void gemm_bias_act_sm_kernel<0, false, 0>(const bf16_t*, const bf16_t*, const float*, bf16_t*, const bf16_t*, int, int, int);
-template __global__ void gemm_bias_act_sm_kernel<1, false, 0>(const bf16_t*, const bf16_t*, const float*, bf16_t*, const bf16_t*, int, int, int);
-template __global__ void gemm_bias_act_sm_kernel<2, false, 0>(const bf16_t*, const bf16_t*, const float*, bf16_t*, const bf16_t*, int, int, int);
-template __global__ void gemm_bias_act_sm_kernel<0, true, 0>(const bf16_t*, const bf16_t*, const float*, bf16_t*, const bf16_t*, int, int, int);
-template __global__ void gemm_bias_act_sm_kernel<0, true, 1>(const bf16_t*, const bf16_t*, const float*, bf16_t*, const bf16_t*, int, int, int);
-template __global__ void gemm_bias_act_sm_kernel<0, true, 2>(const bf16_t*, const bf16_t*, const float*, bf16_t*, const bf16_t*, int, int, int);
+template __global__ void gemm_bias_act_sm_kernel<0, false, 0>(const bf16_t*, const bf16_t*, const float*, bf16_t*, const bf16_t*, int, int, int, const int*);
+template __global__ void gemm_bias_act_sm_kernel<1, false, 0>(const bf16_t*, const bf16_t*, const float*, bf16_t*, const bf16_t*, int, int, int, const int*);
+template __global__ void gemm_bias_act_sm_kernel<2, false, 0>(const bf16_t*, const bf16_t*, const float*, bf16_t*, const bf16_t*, int, int, int, const int*);
+template __global__ void gemm_bias_act_sm_kernel<0, true, 0>(const bf16_t*, const bf16_t*, const float*, bf16_t*, const bf16_t*, int, int, int, const int*);
+template __global__ void gemm_bias_act_sm_kernel<0, true, 1>(const bf16_t*, const bf16_t*, const float*, bf16_t*, const bf16_t*, int, int, int, const int*);
+template __global__ void gemm_bias_act_sm_kernel<0, true, 2>(const bf16_t*, const bf16_t*, const float*, bf16_t*, const bf16_t*, int, int, int, const int*);
 
 // ---------------------------------------------------------------------------
 // N == 1 path (attention gate, CBF head): ONE THREAD per output row — the
@@ -257,8 +271,12 @@ template <int ACT>
 __launch_bounds__(256) __global__
 void dot_bias_act_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ W,
                          const float* __restrict__ bias, float* __restrict__ Y,
-                         long M, int K) {
+                         long M, int K, const int* __restrict__ m_dev) {
   const long m = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (m_dev != nullptr) {
+    const long md = *m_dev;
+    M = md < M ? md : M;
+  }
   if (m >= M) return;
   float a0 = 0.f, a1 = 0.f;
   const int kv = ((K & 7) == 0) ? (K / 16) * 16 : 0;  // b128 path needs 16-B
@@ -276,9 +294,9 @@ void dot_bias_act_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict_
   Y[m] = apply_act(a0 + a1 + bias[0], ACT);
 }
 
-template __global__ void dot_bias_act_kernel<0>(const bf16_t*, const bf16_t*, const float*, float*, long, int);
-template __global__ void dot_bias_act_kernel<1>(const bf16_t*, const bf16_t*, const float*, float*, long, int);
-template __global__ void dot_bias_act_kernel<2>(const bf16_t*, const bf16_t*, const float*, float*, long, int);
+template __global__ void dot_bias_act_kernel<0>(const bf16_t*, const bf16_t*, const float*, float*, long, int, const int*);
+template __global__ void dot_bias_act_kernel<1>(const bf16_t*, const bf16_t*, const float*, float*, long, int, const int*);
+template __global__ void dot_bias_act_kernel<2>(const bf16_t*, const bf16_t*, const float*, float*, long, int, const int*);
 
 // ---------------------------------------------------------------------------
 // Small-N path (N <= 16): one wave per output row, W cached in LDS.
@@ -288,9 +306,11 @@ template <int ACT, typename OutT>
 __launch_bounds__(256) __global__
 void gemv_bias_act_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ W,
                           const float* __restrict__ bias, OutT* __restrict__ Y,
-                          int M, int N, int K) {
+                          int M, int N, int K, const int* __restrict__ m_dev) {
   extern __shared__ char smem[];
   bf16_t* sW = (bf16_t*)smem;  // [K][N]
+  M = live_rows(m_dev, M);
+  if ((long)blockIdx.x * 4 >= M) return;  // block-uniform, ahead of the barrier
   for (int i = threadIdx.x; i < K * N; i += 256) sW[i] = W[i];
   __syncthreads();
 
@@ -356,6 +376,20 @@ __device__ __forceinline__ void tn1_decode_remap(int id, int K, int N, int& kb, 
   nb = j % gn;
 }
 
+// Optional row map of the dW kernels (edge compaction): the reduction runs
+// over the M = numel(row_map) DENSE slot rows, slab and tile boundaries and the
+// position of every row in its MFMA step as in the dense call, but row m is
+// read from row row_map[m] of the compact operands (X, dZ, Yact, rowgate;
+// xrows rows) and is zero where row_map[m] < 0. A masked slot's dZ row is
+// exactly zero in the dense call, so every partial keeps the dense call's bits.
+__device__ __forceinline__ void tn_map_row(const int* __restrict__ row_map, int xrows, long& mr,
+                                           bool& live) {
+  if (row_map == nullptr || !live) return;
+  const int j = row_map[mr];
+  live = j >= 0 && j < xrows;
+  mr = live ? j : 0;
+}
+
 // One block of the tn1 partial: output tile (kb, nb) of split-M slab s.
 template <int ACT>
 __device__ __forceinline__
@@ -367,7 +401,8 @@ void gemm_tn_partial_body(const bf16_t* __restrict__ X, const bf16_t* __restrict
                           // implements per-sample stop-gradient of the
                           // parameters (GCBF+ unlabeled h_dot rows)
                           float* __restrict__ partial, float* __restrict__ db_partial,
-                          int M, int N, int K, int S, int kb, int nb, int s, Tn1Lds& lds) {
+                          int M, int N, int K, int S, int kb, int nb, int s, Tn1Lds& lds,
+                          const int* __restrict__ row_map = nullptr, int xrows = 0) {
   // 64x64 output tile, BMR=64 reduction steps with register-prefetch
   // staging (load tile t+1 into registers while tile t computes).
   constexpr int BKDIM = 64, BN = 64, BMR = 64;
@@ -402,22 +437,24 @@ void gemm_tn_partial_body(const bf16_t* __restrict__ X, const bf16_t* __restrict
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int c = tid + h * 256;
-      const long mr = m0 + (c >> 3);
+      long mr = m0 + (c >> 3);
       const int kc = (c & 7) * 8;
+      bool live = mr < me;
+      tn_map_row(row_map, xrows, mr, live);
       // b128 loads need 16-B alignment: row base mr*K is aligned only when
       // K % 8 == 0 (misaligned b128 at a segment end page-faults)
-      if (mr < me && k0 + kc + 7 < K && (K & 7) == 0) {
+      if (live && k0 + kc + 7 < K && (K & 7) == 0) {
         *(bf16x8*)xv[h] = *(const bf16x8*)(X + mr * K + k0 + kc);
       } else {
 #pragma unroll
         for (int i = 0; i < 8; ++i)
-          xv[h][i] = (mr < me && k0 + kc + i < K) ? X[mr * K + k0 + kc + i] : (bf16_t)0.f;
+          xv[h][i] = (live && k0 + kc + i < K) ? X[mr * K + k0 + kc + i] : (bf16_t)0.f;
       }
-      const bool gated = rowgate != nullptr && mr < me && !rowgate[mr];
+      const bool gated = rowgate != nullptr && live && !rowgate[mr];
       if (gated) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) zv[h][i] = (bf16_t)0.f;
-      } else if (mr < me && n0 + kc + 7 < N && (N & 7) == 0) {
+      } else if (live && n0 + kc + 7 < N && (N & 7) == 0) {
         *(bf16x8*)zv[h] = *(const bf16x8*)(dZ + mr * N + n0 + kc);
         if constexpr (ACT != 0) {
           // dZ operand is dY here: fold dZ = dY * act'(Y) into the stage
@@ -429,7 +466,7 @@ void gemm_tn_partial_body(const bf16_t* __restrict__ X, const bf16_t* __restrict
       } else {
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-          const bool ok = mr < me && n0 + kc + i < N;
+          const bool ok = live && n0 + kc + i < N;
           float z = ok ? (float)dZ[mr * N + n0 + kc + i] : 0.f;
           if constexpr (ACT != 0)
             if (ok) z *= act_grad_from_out((float)Yact[mr * N + n0 + kc + i], ACT);
@@ -512,8 +549,13 @@ __launch_bounds__(256) __global__
 void gemm_tn_partial_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ dZ,
                             const bf16_t* __restrict__ Yact, const bool* __restrict__ rowgate,
                             float* __restrict__ partial, float* __restrict__ db_partial,
-                            int M, int N, int K, int S, int remap) {
+                            int M, int N, int K, int S, int remap,
+                            const int* __restrict__ m_dev, const int* __restrict__ row_map,
+                            int xrows) {
   __shared__ Tn1Lds lds;
+  // a device row count moves the slab boundaries (m_per below); every slab
+  // still writes its partial, the empty ones zeros
+  M = live_rows(m_dev, M);
   int kb, nb, s;
   if (remap) {
     tn1_decode_remap(blockIdx.x, K, N, kb, nb, s);
@@ -522,7 +564,8 @@ void gemm_tn_partial_kernel(const bf16_t* __restrict__ X, const bf16_t* __restri
     nb = blockIdx.y;
     s = blockIdx.z;
   }
-  gemm_tn_partial_body<ACT>(X, dZ, Yact, rowgate, partial, db_partial, M, N, K, S, kb, nb, s, lds);
+  gemm_tn_partial_body<ACT>(X, dZ, Yact, rowgate, partial, db_partial, M, N, K, S, kb, nb, s, lds,
+                            row_map, xrows);
 }
 
 // Several independent tn1 problems in one launch (deferred-dW flush). A block
@@ -560,9 +603,9 @@ void gemm_tn_partial_grouped_kernel(const TnPartialGroup g) {
     gemm_tn_partial_body<0>(X, dZ, Yact, p.rowgate, p.partial, p.db_partial, M, N, K, S, kb, nb, s, lds);
 }
 
-template __global__ void gemm_tn_partial_kernel<0>(const bf16_t*, const bf16_t*, const bf16_t*, const bool*, float*, float*, int, int, int, int, int);
-template __global__ void gemm_tn_partial_kernel<1>(const bf16_t*, const bf16_t*, const bf16_t*, const bool*, float*, float*, int, int, int, int, int);
-template __global__ void gemm_tn_partial_kernel<2>(const bf16_t*, const bf16_t*, const bf16_t*, const bool*, float*, float*, int, int, int, int, int);
+template __global__ void gemm_tn_partial_kernel<0>(const bf16_t*, const bf16_t*, const bf16_t*, const bool*, float*, float*, int, int, int, int, int, const int*, const int*, int);
+template __global__ void gemm_tn_partial_kernel<1>(const bf16_t*, const bf16_t*, const bf16_t*, const bool*, float*, float*, int, int, int, int, int, const int*, const int*, int);
+template __global__ void gemm_tn_partial_kernel<2>(const bf16_t*, const bf16_t*, const bf16_t*, const bool*, float*, float*, int, int, int, int, int, const int*, const int*, int);
 
 // ---------------------------------------------------------------------------
 // dW computed TRANSPOSED: dW^T[n,k] = sum_m dZ[m,n] X[m,k]. With i=n, j=k,
@@ -619,9 +662,14 @@ void gemm_tn_partial3_kernel(const bf16_t* __restrict__ X, const bf16_t* __restr
                              const bf16_t* __restrict__ Yact,
                              const bool* __restrict__ rowgate,
                              float* __restrict__ partial, float* __restrict__ db_partial,
-                             int M, int N, int K, int S, int remap) {
+                             int M, int N, int K, int S, int remap,
+                             const int* __restrict__ m_dev, const int* __restrict__ row_map,
+                             int xrows) {
   constexpr int BNR = 64, BKD = 64, BMR = 64;
   constexpr int TILE = BMR * 64;  // elements of one row-major tile
+  // a device row count moves the slab boundaries (m_per below): the live rows
+  // spread over all S slabs, and an empty slab still writes a zero partial
+  M = live_rows(m_dev, M);
   // one array for all LDS: dZ tile | X tile | db exchange
   __shared__ __attribute__((aligned(16))) unsigned char smem[2 * TILE * 2 + 4 * BNR * 4];
   bf16_t* const sZ = (bf16_t*)smem;
@@ -674,20 +722,22 @@ void gemm_tn_partial3_kernel(const bf16_t* __restrict__ X, const bf16_t* __restr
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int c = tid + h * 256;
-      const long mr = m0 + (c >> 3);
+      long mr = m0 + (c >> 3);
       const int cc = (c & 7) * 8;
-      if (mr < me && xvec && k0 + cc + 7 < K) {
+      bool live = mr < me;
+      tn_map_row(row_map, xrows, mr, live);
+      if (live && xvec && k0 + cc + 7 < K) {
         *(bf16x8*)xv[h] = *(const bf16x8*)(X + mr * K + k0 + cc);
       } else {
 #pragma unroll
         for (int i = 0; i < 8; ++i)
-          xv[h][i] = (mr < me && k0 + cc + i < K) ? X[mr * K + k0 + cc + i] : (bf16_t)0.f;
+          xv[h][i] = (live && k0 + cc + i < K) ? X[mr * K + k0 + cc + i] : (bf16_t)0.f;
       }
-      const bool zgated = rowgate != nullptr && mr < me && !rowgate[mr];
+      const bool zgated = rowgate != nullptr && live && !rowgate[mr];
       if (zgated) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) zv[h][i] = (bf16_t)0.f;
-      } else if (mr < me && zvec && n0 + cc + 7 < N) {
+      } else if (live && zvec && n0 + cc + 7 < N) {
         *(bf16x8*)zv[h] = *(const bf16x8*)(dZ + mr * N + n0 + cc);
         if constexpr (ACT != 0) {
           bf16x8 yv = *(const bf16x8*)(Yact + mr * N + n0 + cc);
@@ -698,7 +748,7 @@ void gemm_tn_partial3_kernel(const bf16_t* __restrict__ X, const bf16_t* __restr
       } else {
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-          const bool ok = mr < me && n0 + cc + i < N;
+          const bool ok = live && n0 + cc + i < N;
           float z = ok ? (float)dZ[mr * N + n0 + cc + i] : 0.f;
           if constexpr (ACT != 0)
             if (ok) z *= act_grad_from_out((float)Yact[mr * N + n0 + cc + i], ACT);
@@ -793,9 +843,9 @@ void gemm_tn_partial3_kernel(const bf16_t* __restrict__ X, const bf16_t* __restr
   }
 }
 
-template __global__ void gemm_tn_partial3_kernel<0>(const bf16_t*, const bf16_t*, const bf16_t*, const bool*, float*, float*, int, int, int, int, int);
-template __global__ void gemm_tn_partial3_kernel<1>(const bf16_t*, const bf16_t*, const bf16_t*, const bool*, float*, float*, int, int, int, int, int);
-template __global__ void gemm_tn_partial3_kernel<2>(const bf16_t*, const bf16_t*, const bf16_t*, const bool*, float*, float*, int, int, int, int, int);
+template __global__ void gemm_tn_partial3_kernel<0>(const bf16_t*, const bf16_t*, const bf16_t*, const bool*, float*, float*, int, int, int, int, int, const int*, const int*, int);
+template __global__ void gemm_tn_partial3_kernel<1>(const bf16_t*, const bf16_t*, const bf16_t*, const bool*, float*, float*, int, int, int, int, int, const int*, const int*, int);
+template __global__ void gemm_tn_partial3_kernel<2>(const bf16_t*, const bf16_t*, const bf16_t*, const bool*, float*, float*, int, int, int, int, int, const int*, const int*, int);
 
 // ---------------------------------------------------------------------------
 // dW^T orientation at 128x128 block / 64x64 wave tile: same vector-only
@@ -1186,18 +1236,18 @@ void reduce_dw_db_grouped_kernel(const DwReduceGroup g) {
 // ---------------------------------------------------------------------------
 // host-visible launchers (called from bindings.cpp)
 // ---------------------------------------------------------------------------
-template __global__ void gemm_bias_act_kernel<0, false, 0>(const bf16_t*, const bf16_t*, const float*, bf16_t*, const bf16_t*, int, int, int);
-template __global__ void gemm_bias_act_kernel<1, false, 0>(const bf16_t*, const bf16_t*, const float*, bf16_t*, const bf16_t*, int, int, int);
-template __global__ void gemm_bias_act_kernel<2, false, 0>(const bf16_t*, const bf16_t*, const float*, bf16_t*, const bf16_t*, int, int, int);
-template __global__ void gemm_bias_act_kernel<0, true, 0>(const bf16_t*, const bf16_t*, const float*, bf16_t*, const bf16_t*, int, int, int);
-template __global__ void gemm_bias_act_kernel<0, true, 1>(const bf16_t*, const bf16_t*, const float*, bf16_t*, const bf16_t*, int, int, int);
-template __global__ void gemm_bias_act_kernel<0, true, 2>(const bf16_t*, const bf16_t*, const float*, bf16_t*, const bf16_t*, int, int, int);
-template __global__ void gemv_bias_act_kernel<0, bf16_t>(const bf16_t*, const bf16_t*, const float*, bf16_t*, int, int, int);
-template __global__ void gemv_bias_act_kernel<1, bf16_t>(const bf16_t*, const bf16_t*, const float*, bf16_t*, int, int, int);
-template __global__ void gemv_bias_act_kernel<2, bf16_t>(const bf16_t*, const bf16_t*, const float*, bf16_t*, int, int, int);
-template __global__ void gemv_bias_act_kernel<0, float>(const bf16_t*, const bf16_t*, const float*, float*, int, int, int);
-template __global__ void gemv_bias_act_kernel<1, float>(const bf16_t*, const bf16_t*, const float*, float*, int, int, int);
-template __global__ void gemv_bias_act_kernel<2, float>(const bf16_t*, const bf16_t*, const float*, float*, int, int, int);
+template __global__ void gemm_bias_act_kernel<0, false, 0>(const bf16_t*, const bf16_t*, const float*, bf16_t*, const bf16_t*, int, int, int, const int*);
+template __global__ void gemm_bias_act_kernel<1, false, 0>(const bf16_t*, const bf16_t*, const float*, bf16_t*, const bf16_t*, int, int, int, const int*);
+template __global__ void gemm_bias_act_kernel<2, false, 0>(const bf16_t*, const bf16_t*, const float*, bf16_t*, const bf16_t*, int, int, int, const int*);
+template __global__ void gemm_bias_act_kernel<0, true, 0>(const bf16_t*, const bf16_t*, const float*, bf16_t*, const bf16_t*, int, int, int, const int*);
+template __global__ void gemm_bias_act_kernel<0, true, 1>(const bf16_t*, const bf16_t*, const float*, bf16_t*, const bf16_t*, int, int, int, const int*);
+template __global__ void gemm_bias_act_kernel<0, true, 2>(const bf16_t*, const bf16_t*, const float*, bf16_t*, const bf16_t*, int, int, int, const int*);
+template __global__ void gemv_bias_act_kernel<0, bf16_t>(const bf16_t*, const bf16_t*, const float*, bf16_t*, int, int, int, const int*);
+template __global__ void gemv_bias_act_kernel<1, bf16_t>(const bf16_t*, const bf16_t*, const float*, bf16_t*, int, int, int, const int*);
+template __global__ void gemv_bias_act_kernel<2, bf16_t>(const bf16_t*, const bf16_t*, const float*, bf16_t*, int, int, int, const int*);
+template __global__ void gemv_bias_act_kernel<0, float>(const bf16_t*, const bf16_t*, const float*, float*, int, int, int, const int*);
+template __global__ void gemv_bias_act_kernel<1, float>(const bf16_t*, const bf16_t*, const float*, float*, int, int, int, const int*);
+template __global__ void gemv_bias_act_kernel<2, float>(const bf16_t*, const bf16_t*, const float*, float*, int, int, int, const int*);
 
 // ---------------------------------------------------------------------------
 // Row-panel GEMM (dispatch names "glds" / "glds_bt"): one workgroup owns 128
@@ -1391,8 +1441,12 @@ template <int ACT, bool BT, int NCH>
 __launch_bounds__(256) __global__
 void gemm_bias_act_panel_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ W,
                                 const float* __restrict__ bias, bf16_t* __restrict__ Y,
-                                int M, int N, int nbuf, int wvec) {
+                                int M, int N, int nbuf, int wvec,
+                                const int* __restrict__ m_dev) {
   constexpr int BM = 128, BN = 64, K = NCH * 64;
+  // a device row count is a multiple of 128 here (the caller hands the padded
+  // count): panels past it leave ahead of every DMA, barrier and LDS write
+  if ((int)blockIdx.x * BM >= live_rows(m_dev, M)) return;
   extern __shared__ char smem[];
   bf16_t* const sA = (bf16_t*)smem;  // [NCH][128][64]
   bf16_t* const sW = sA + BM * K;    // nbuf x (64 * K)
@@ -1536,12 +1590,12 @@ void gemm_bias_act_panel_kernel(const bf16_t* __restrict__ X, const bf16_t* __re
 }
 
 #define PANEL_INST(ACT, BT)                                                                          \
-  template __global__ void gemm_bias_act_panel_kernel<ACT, BT, 1>(const bf16_t*, const bf16_t*, const float*, bf16_t*, int, int, int, int); \
-  template __global__ void gemm_bias_act_panel_kernel<ACT, BT, 2>(const bf16_t*, const bf16_t*, const float*, bf16_t*, int, int, int, int); \
-  template __global__ void gemm_bias_act_panel_kernel<ACT, BT, 3>(const bf16_t*, const bf16_t*, const float*, bf16_t*, int, int, int, int); \
-  template __global__ void gemm_bias_act_panel_kernel<ACT, BT, 4>(const bf16_t*, const bf16_t*, const float*, bf16_t*, int, int, int, int); \
-  template __global__ void gemm_bias_act_panel_kernel<ACT, BT, 5>(const bf16_t*, const bf16_t*, const float*, bf16_t*, int, int, int, int); \
-  template __global__ void gemm_bias_act_panel_kernel<ACT, BT, 6>(const bf16_t*, const bf16_t*, const float*, bf16_t*, int, int, int, int);
+  template __global__ void gemm_bias_act_panel_kernel<ACT, BT, 1>(const bf16_t*, const bf16_t*, const float*, bf16_t*, int, int, int, int, const int*); \
+  template __global__ void gemm_bias_act_panel_kernel<ACT, BT, 2>(const bf16_t*, const bf16_t*, const float*, bf16_t*, int, int, int, int, const int*); \
+  template __global__ void gemm_bias_act_panel_kernel<ACT, BT, 3>(const bf16_t*, const bf16_t*, const float*, bf16_t*, int, int, int, int, const int*); \
+  template __global__ void gemm_bias_act_panel_kernel<ACT, BT, 4>(const bf16_t*, const bf16_t*, const float*, bf16_t*, int, int, int, int, const int*); \
+  template __global__ void gemm_bias_act_panel_kernel<ACT, BT, 5>(const bf16_t*, const bf16_t*, const float*, bf16_t*, int, int, int, int, const int*); \
+  template __global__ void gemm_bias_act_panel_kernel<ACT, BT, 6>(const bf16_t*, const bf16_t*, const float*, bf16_t*, int, int, int, int, const int*);
 PANEL_INST(0, false)
 PANEL_INST(1, false)
 PANEL_INST(2, false)

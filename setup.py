@@ -16,6 +16,7 @@ setup(
             sources=[
                 "gcbfplus_amd/ops/hip/gemm.hip",
                 "gcbfplus_amd/ops/hip/softmax_aggr.hip",
+                "gcbfplus_amd/ops/hip/edge_compact.hip",
                 "gcbfplus_amd/ops/hip/raytrace.hip",
                 "gcbfplus_amd/ops/hip/proxqp.hip",
                 "gcbfplus_amd/ops/hip/edge_msg.hip",
