@@ -37,6 +37,8 @@ __global__ void gemm_tn_partial2_kernel(const bf16_t_*, const bf16_t_*, const bf
 template <int ACT>
 __global__ void gemm_tn_partial3_kernel(const bf16_t_*, const bf16_t_*, const bf16_t_*, const bool*, float*, float*, int, int, int, int, int, const int*, const int*, int);
 template <int ACT>
+__global__ void gemm_tn_partial3_map_kernel(const bf16_t_*, const bf16_t_*, const bf16_t_*, const bool*, float*, float*, int, int, int, int, int, const int*, int);
+template <int ACT>
 __global__ void gemm_tn_partial4_kernel(const bf16_t_*, const bf16_t_*, const bf16_t_*, float*, float*, int, int, int, int, int);
 __global__ void softmax_aggr_fwd_kernel(const float*, const bf16_t_*, const bool*, bf16_t_*, float*, int, int);
 __global__ void softmax_aggr_bwd_kernel(const bf16_t_*, const float*, const bf16_t_*, float*, bf16_t_*, int, int);
@@ -319,6 +321,30 @@ std::vector<std::string> gemm_default_paths() {
 
 long gemm_lds_limit_bytes() { return (long)gemm_lds_limit(); }
 
+// A dW call with a row map: tn3 runs the sparse-staged kernel
+// (gemm_tn_partial3_map_kernel) on the same plan. The choice depends on the
+// presence of a map, never on the shape; GCBF_NO_TN_SPARSE=1 (read once)
+// keeps gemm_tn_partial3_kernel's map path as the in-build reference arm.
+static bool tn_sparse_enabled() {
+  static const bool on = [] {
+    const char* e = getenv("GCBF_NO_TN_SPARSE");
+    return !(e && atoi(e) != 0);
+  }();
+  return on;
+}
+
+// Launch-free query for a dW call through a row map of M entries:
+// "tn3map S=.. remap=..", "tn3 .." under GCBF_NO_TN_SPARSE, or "tn1 ..".
+std::string gemm_tn_map_path(long M, long K, long N, long actin, bool gated) {
+  TORCH_CHECK(M > 0 && K > 0 && N > 0, "gemm_tn_map_path: M, K, N must be positive");
+  GemmPlan p = gemm_plan(GEMM_TN, M, K, N, actin, gated);
+  TORCH_CHECK(p.kernel == GK_TN1 || p.kernel == GK_TN3,
+              "dW with row_map: only the tn1 and tn3 kernels take one");
+  const bool sparse = p.kernel == GK_TN3 && tn_sparse_enabled();
+  return std::string(sparse ? "tn3map" : gemm_kernel_name(p.kernel)) + " S=" +
+         std::to_string(p.S) + " remap=" + (p.remap ? "1" : "0");
+}
+
 // Row-panel kernel launch ("glds" / "glds_bt"). Its LDS request exceeds
 // 64 KiB from K = 192 on, so each instantiation raises its dynamic-LDS
 // ceiling once per device: a function attribute, not a stream operation, so
@@ -597,6 +623,20 @@ static void tn_launch_partial(TnCall& c, const torch::Tensor& x, const torch::Te
     if (actin == 1) launch24(gemm_tn_partial2_kernel<1>);
     else if (actin == 2) launch24(gemm_tn_partial2_kernel<2>);
     else launch24(gemm_tn_partial2_kernel<0>);
+  } else if (plan.kernel == GK_TN3 && c.rmap != nullptr && tn_sparse_enabled()) {
+    const size_t limit = gemm_lds_limit();
+    TORCH_CHECK((size_t)TN3MAP_LDS <= limit, "gemm_tn with row_map: M=", M, " K=", K, " N=", N,
+                " (tn3map kernel) needs ", (size_t)TN3MAP_LDS, " bytes of LDS, device limit ", limit);
+    auto launch_map = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, remap ? dim3(gk * gn * S) : dim3(gk, gn, S), dim3(256), 0,
+                         stream, bfp(x), bfp(dz), ya, rg, c.partial.data_ptr<float>(),
+                         c.db_partial.data_ptr<float>(), (int)M, (int)N, (int)K, (int)S,
+                         remap ? 1 : 0, c.rmap, c.xrows);
+      C10_HIP_KERNEL_LAUNCH_CHECK();
+    };
+    if (actin == 1) launch_map(gemm_tn_partial3_map_kernel<1>);
+    else if (actin == 2) launch_map(gemm_tn_partial3_map_kernel<2>);
+    else launch_map(gemm_tn_partial3_map_kernel<0>);
   } else if (plan.kernel == GK_TN3) {
     if (actin == 1) launch(gemm_tn_partial3_kernel<1>);
     else if (actin == 2) launch(gemm_tn_partial3_kernel<2>);
@@ -1779,6 +1819,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("gated") = false);
   m.def("gemm_default_paths", &gemm_default_paths,
         "every gemm_path a default environment can select (dW slab count left out)");
+  m.def("gemm_tn_map_path", &gemm_tn_map_path,
+        "kernel a dW call through a row map of M entries selects (no launch)",
+        py::arg("M"), py::arg("K"), py::arg("N"), py::arg("actin") = 0, py::arg("gated") = false);
   m.def("gemm_lds_limit", &gemm_lds_limit_bytes,
         "dynamic LDS bytes a workgroup may request on the current device");
   m.def("act_bwd", &act_bwd, "dZ = dY * act'(Y)");

@@ -50,5 +50,19 @@ struct DwReduceGroup {
   DwReduceProblem p[DW_GROUP_MAX];
 };
 
+// Geometry of the sparse-staged dW kernel (gemm_tn_partial3_map_kernel): a
+// chunk holds up to TN3MAP_ROWS live operand rows and spans up to
+// TN3MAP_TILES dense 64-row tiles. LDS: two compact images of ROWS + 1 rows
+// (the last is the shared zero row) of 128 bytes, the row table (one 16-bit
+// entry per dense row plus one step of read-ahead), the source row of every
+// slot, the per-tile counts and the db exchange.
+#define TN3MAP_ROWS 128
+#define TN3MAP_TILES 16
+#define TN3MAP_LDS                                                                  \
+  (2 * (TN3MAP_ROWS + 1) * 128 + (2 * TN3MAP_TILES + 1) * 32 * 2 + TN3MAP_ROWS * 4 + \
+   TN3MAP_TILES * 4 + 4 * 64 * 4)
+static_assert(TN3MAP_ROWS >= 64 && TN3MAP_ROWS < 65535, "a chunk must hold one full tile");
+static_assert(TN3MAP_TILES % 4 == 0, "one wave numbers one tile per pass");
+
 static_assert(sizeof(TnPartialGroup) <= 2048, "grouped partial table must stay under 2 KB");
 static_assert(sizeof(DwReduceGroup) <= 2048, "grouped reduce table must stay under 2 KB");

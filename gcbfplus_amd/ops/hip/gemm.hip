@@ -30,7 +30,8 @@
 // of the static M, so edge-compacted calls replay from a captured graph with
 // any count (edge_compact.hip). With m_dev null nothing changes. Training
 // gives tn1 / tn3 a row map instead (tn_map_row): the dense call's summation
-// order over compact operands, so dW/db keep the dense call's bits.
+// order over compact operands, so dW/db keep the dense call's bits. With a
+// map tn3 runs gemm_tn_partial3_map_kernel, which stages the live rows only.
 #include "common.h"
 #include "dw_group.h"
 
@@ -846,6 +847,300 @@ void gemm_tn_partial3_kernel(const bf16_t* __restrict__ X, const bf16_t* __restr
 template __global__ void gemm_tn_partial3_kernel<0>(const bf16_t*, const bf16_t*, const bf16_t*, const bool*, float*, float*, int, int, int, int, int, const int*, const int*, int);
 template __global__ void gemm_tn_partial3_kernel<1>(const bf16_t*, const bf16_t*, const bf16_t*, const bool*, float*, float*, int, int, int, int, int, const int*, const int*, int);
 template __global__ void gemm_tn_partial3_kernel<2>(const bf16_t*, const bf16_t*, const bf16_t*, const bool*, float*, float*, int, int, int, int, int, const int*, const int*, int);
+
+// ---------------------------------------------------------------------------
+// gemm_tn_partial3_kernel for a call with a row map, staged sparse. With a map
+// nine in ten rows of every dense tile are zeros, and the tile loop above is a
+// latency chain (map load -> operand load -> barrier -> LDS write -> barrier).
+// Here a block takes its slab in chunks of whole 64-row dense tiles: it reads
+// the chunk's map segment, numbers the in-range entries in order of
+// appearance (one wave ballot per tile), loads only those operand rows, all
+// at once, into a COMPACT LDS image, and then runs the dense call's MFMA
+// steps with no barrier and no global access: in ds_read_b64_tr_b16 every
+// lane supplies its own row address, so a lane whose dense row is live points
+// at that row's compact copy and a lane whose dense row is masked points at
+// one shared all-zero row. A 16-bit table holds the LDS row slot of every
+// dense row of the chunk, the two entries a lane needs in one step adjacent.
+//
+// The partials are bit-equal to gemm_tn_partial3_kernel's because
+//  1. the launch geometry is the same: plan (gk, gn, S, remap) from the 64x64
+//     tiling of the dense M = numel(row_map), the same XCD remap of the block
+//     id, the same slab bounds m_per = ceil(M/S), ms, me; an empty slab writes
+//     a zero partial and a zero db_partial;
+//  2. the MFMA work is the same: per output element one
+//     v_mfma_f32_16x16x32_bf16 per 32 dense rows, in increasing order from ms,
+//     the zero-filled tail of the last 64-row tile included, from a zero
+//     accumulator. No masked row is dropped and no row moves inside its step;
+//  3. the operand positions are the same: dense row ms + 64t + 32mm + 8g + e
+//     is element e of lane group g in both operands (tn3_read_frag);
+//  4. the staged values are the same: a live row holds the bits load_tile
+//     produces (dZ folded with act_grad_from_out(Yact) in f32 and rounded to
+//     bf16, zeroed where rowgate[j] is false; ragged K/N columns zero-filled,
+//     never masked; b128 loads only under xvec / zvec, scalar otherwise); a map
+//     entry < 0 or >= xrows is a masked row;
+//  5. the db order is the same: thread (db_q, db_c) adds the rows with
+//     ((m - ms) % 64) / 16 == db_q in increasing m into one f32 that starts at
+//     +0, and the four sums combine as (s0+s1)+(s2+s3). Masked rows are read
+//     from the zero row here; they could as well be skipped, since adding +0
+//     to an accumulator that is never -0 is exact.
+// A chunk takes as many tiles (<= TN3MAP_TILES) as its live rows fit
+// TN3MAP_ROWS slots, at least one (ROWS >= 64), so any density runs, 100%
+// included. The numbering does not need a monotonic map. Image rows use the
+// swizzle of the dense tile (tn3_off) on the slot number: consecutive slots,
+// which is what a half-wave's live rows mostly are, spread like consecutive
+// dense rows. EXEC is full around every transposed read (all trip counts are
+// block-uniform) and every address is 8-byte aligned.
+// ---------------------------------------------------------------------------
+template <int ACT>
+__launch_bounds__(256) __global__
+void gemm_tn_partial3_map_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ dZ,
+                                 const bf16_t* __restrict__ Yact,
+                                 const bool* __restrict__ rowgate,
+                                 float* __restrict__ partial, float* __restrict__ db_partial,
+                                 int M, int N, int K, int S, int remap,
+                                 const int* __restrict__ row_map, int xrows) {
+  constexpr int BNR = 64, BKD = 64, BMR = 64;
+  constexpr int C = TN3MAP_ROWS, TT = TN3MAP_TILES;
+  constexpr int IMG = (C + 1) * 64;  // elements of one compact image, zero row last
+  __shared__ __attribute__((aligned(16))) unsigned char smem[TN3MAP_LDS];
+  bf16_t* const sZ = (bf16_t*)smem;
+  bf16_t* const sX = sZ + IMG;
+  unsigned short* const sTab = (unsigned short*)(sX + IMG);
+  int* const sSrc = (int*)(sTab + (2 * TT + 1) * 32);
+  int* const sCnt = sSrc + C;
+  float* const sDb = (float*)(sCnt + TT);
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int w = tid >> 6;
+  const int wi = w >> 1, wj = w & 1;  // wave tile 32(n) x 32(k)
+  int kb, nb, s;
+  if (remap) {
+    const int gk = (K + BKD - 1) / BKD, gn = (N + BNR - 1) / BNR;
+    const int per = gk * gn;
+    const int id = blockIdx.x;
+    const int rest = id >> 3;
+    s = (id & 7) + 8 * (rest / per);
+    const int j = rest % per;
+    kb = j / gn;
+    nb = j % gn;
+  } else {
+    kb = blockIdx.x;
+    nb = blockIdx.y;
+    s = blockIdx.z;
+  }
+  const int k0 = kb * BKD;
+  const int n0 = nb * BNR;
+
+  const long m_per = ((long)M + S - 1) / S;
+  const long ms = (long)s * m_per;
+  const long me = (ms + m_per < (long)M) ? ms + m_per : (long)M;
+  const int ntiles = me > ms ? (int)((me - ms + BMR - 1) / BMR) : 0;
+
+  f32x4 acc[2][2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float db_acc = 0.f;
+  const int db_c = tid & 63, db_q = tid >> 6;
+
+  const bool xvec = (K & 7) == 0 && ((size_t)X & 15) == 0;
+  const bool zvec = (N & 7) == 0 && ((size_t)dZ & 15) == 0 &&
+                    (ACT == 0 || ((size_t)Yact & 15) == 0);
+
+  // the zero row; the chunk barriers order it before the first read
+  if (tid < 16) {
+    bf16x8 z;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) z[i] = (bf16_t)0.f;
+    *(bf16x8*)((tid < 8 ? sZ : sX) + C * 64 + (tid & 7) * 8) = z;
+  }
+
+  // lane 4q+p of a 16-lane group points at row q, columns 4p..4p+3 of its
+  // block, as in gemm_tn_partial3_kernel; the row is now a slot from the table
+  const int g = lane >> 4, tq = (lane >> 2) & 3, tp = lane & 3;
+  const int tl = g * 4 + tq;  // the lane's pair of table entries in a step
+  const int e4 = 4 * (tp & 1);
+  const int cha = wi * 4 + (tp >> 1), chb = wj * 4 + (tp >> 1), chd = g * 2 + (tp >> 1);
+  const unsigned* const tab32 = (const unsigned*)sTab;
+  typedef short s16x8 __attribute__((ext_vector_type(8)));
+  auto read_frag = [&](const bf16_t* img, int s0, int s1, int ch) {
+    const tn3_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((tn3_lds_s16x4*)(img + tn3_off(s0, ch) + e4));
+    const tn3_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((tn3_lds_s16x4*)(img + tn3_off(s1, ch) + e4));
+    const s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+    return __builtin_bit_cast(bf16x8, v);
+  };
+
+  for (int t0 = 0; t0 < ntiles;) {
+    const int tleft = ntiles - t0 < TT ? ntiles - t0 : TT;
+    const long mc = ms + (long)t0 * BMR;
+
+    // map segment: wave w takes tiles w, w+4, ..; a tile is one ballot
+    int jrow[TT / 4], within[TT / 4];
+#pragma unroll
+    for (int i = 0; i < TT / 4; ++i) {
+      const int tile = 4 * i + w;
+      const long m = mc + (long)tile * BMR + lane;
+      int j = -1;
+      if (tile < tleft && m < me) j = row_map[m];
+      const bool live = j >= 0 && j < xrows;
+      const unsigned long long mask = __ballot(live);
+      within[i] = __popcll(mask & ((1ull << lane) - 1ull));
+      jrow[i] = live ? j : -1;
+      if (lane == 0) sCnt[tile] = __popcll(mask);
+    }
+    __syncthreads();  // counts visible; every wave has left the previous chunk
+
+    // tiles of this chunk: the longest prefix whose live rows fit C slots
+    int run = 0, nt = 0, pre[TT / 4];
+    bool open = true;
+#pragma unroll
+    for (int t = 0; t < TT; ++t) {
+      const int c = sCnt[t];
+      open = open && t < tleft && run + c <= C;
+      if ((t & 3) == w) pre[t >> 2] = run;
+      if (open) {
+        run += c;
+        nt = t + 1;
+      }
+    }
+    const int nrows = run;
+#pragma unroll
+    for (int i = 0; i < TT / 4; ++i) {
+      const int tile = 4 * i + w;
+      if (tile < nt) {
+        // dense row 32*step + 8*g + 4*h + q of the chunk -> entry
+        // 32*step + 2*(4*g + q) + h: one 32-bit read gives a lane both rows
+        const int slot = jrow[i] >= 0 ? pre[i] + within[i] : C;
+        const int r32 = lane & 31;
+        const int e = (tile * 2 + (lane >> 5)) * 32 + (((r32 >> 3) * 4 + (r32 & 3)) << 1) +
+                      ((r32 >> 2) & 1);
+        sTab[e] = (unsigned short)slot;
+        if (jrow[i] >= 0) sSrc[slot] = jrow[i];
+      }
+    }
+    __syncthreads();
+
+    // operand rows of the chunk, 16-byte chunk c & 7 of slot c >> 3: all
+    // addresses are known, so the loads go out together; act fold and row
+    // gate in registers as in load_tile
+    constexpr int NH = C * 8 / 256;
+    bf16_t xv[NH][8], zv[NH][8];
+#pragma unroll
+    for (int h = 0; h < NH; ++h) {
+      const int c = tid + h * 256;
+      const int slot = c >> 3;
+      const int cc = (c & 7) * 8;
+      const bool live = slot < nrows;
+      const long mr = live ? sSrc[slot] : 0;
+      if (live && xvec && k0 + cc + 7 < K) {
+        *(bf16x8*)xv[h] = *(const bf16x8*)(X + mr * K + k0 + cc);
+      } else {
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+          xv[h][i] = (live && k0 + cc + i < K) ? X[mr * K + k0 + cc + i] : (bf16_t)0.f;
+      }
+      const bool zgated = rowgate != nullptr && live && !rowgate[mr];
+      if (zgated) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) zv[h][i] = (bf16_t)0.f;
+      } else if (live && zvec && n0 + cc + 7 < N) {
+        *(bf16x8*)zv[h] = *(const bf16x8*)(dZ + mr * N + n0 + cc);
+        if constexpr (ACT != 0) {
+          bf16x8 yv = *(const bf16x8*)(Yact + mr * N + n0 + cc);
+#pragma unroll
+          for (int i = 0; i < 8; ++i)
+            zv[h][i] = (bf16_t)((float)zv[h][i] * act_grad_from_out((float)yv[i], ACT));
+        }
+      } else {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          const bool ok = live && n0 + cc + i < N;
+          float z = ok ? (float)dZ[mr * N + n0 + cc + i] : 0.f;
+          if constexpr (ACT != 0)
+            if (ok) z *= act_grad_from_out((float)Yact[mr * N + n0 + cc + i], ACT);
+          zv[h][i] = (bf16_t)z;
+        }
+      }
+    }
+#pragma unroll
+    for (int h = 0; h < NH; ++h) {
+      const int c = tid + h * 256;
+      if ((c >> 3) < nrows) {
+        const int o = tn3_off(c >> 3, c & 7);
+        *(bf16x8*)(sZ + o) = *(bf16x8*)zv[h];
+        *(bf16x8*)(sX + o) = *(bf16x8*)xv[h];
+      }
+    }
+    __syncthreads();
+
+    // the dense call's steps over the chunk; table read one step ahead (the
+    // table has one spare step, so the last read-ahead stays inside it)
+    unsigned nxt = tab32[tl];
+    for (int t = 0; t < nt; ++t) {
+      if (kb == 0) {
+        // column db_c, dense rows 16*db_q + 0..15 of the tile in increasing order
+        const unsigned* dp = tab32 + (2 * t + (db_q >> 1)) * 16 + (db_q & 1) * 8 + tq;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const unsigned p = dp[(r >> 1) * 4];
+          const int slot = (r & 1) ? (int)(p >> 16) : (int)(p & 0xffffu);
+          const tn3_s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+              (tn3_lds_s16x4*)(sZ + tn3_off(slot, chd) + e4));
+          typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+          const bf16x4 bv = __builtin_bit_cast(bf16x4, v);
+#pragma unroll
+          for (int i = 0; i < 4; ++i) db_acc += (float)bv[i];
+        }
+      }
+#pragma unroll
+      for (int mm = 0; mm < 2; ++mm) {
+        const unsigned cur = nxt;
+        nxt = tab32[(2 * t + mm + 1) * 16 + tl];
+        const int s0 = (int)(cur & 0xffffu), s1 = (int)(cur >> 16);
+        bf16x8 afr[2], bfr[2];
+#pragma unroll
+        for (int nf = 0; nf < 2; ++nf) afr[nf] = read_frag(sZ, s0, s1, cha + nf * 2);
+#pragma unroll
+        for (int kf = 0; kf < 2; ++kf) bfr[kf] = read_frag(sX, s0, s1, chb + kf * 2);
+#pragma unroll
+        for (int nf = 0; nf < 2; ++nf)
+#pragma unroll
+          for (int kf = 0; kf < 2; ++kf)
+            acc[nf][kf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afr[nf], bfr[kf], acc[nf][kf], 0, 0, 0);
+      }
+    }
+    t0 += nt;
+  }
+
+  if (kb == 0) {
+    sDb[db_q * BNR + db_c] = db_acc;
+    __syncthreads();
+    if (db_q == 0 && n0 + db_c < N)
+      db_partial[(long)s * N + n0 + db_c] =
+          (sDb[db_c] + sDb[BNR + db_c]) + (sDb[2 * BNR + db_c] + sDb[3 * BNR + db_c]);
+  }
+
+  // as gemm_tn_partial3_kernel: transposed into partial[s][k][n]
+  float* out = partial + (long)s * K * N;
+#pragma unroll
+  for (int nf = 0; nf < 2; ++nf) {
+#pragma unroll
+    for (int kf = 0; kf < 2; ++kf) {
+      const int krow = k0 + wj * 32 + kf * 16 + (lane & 15);
+      if (krow >= K) continue;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int ncol = n0 + wi * 32 + nf * 16 + (lane >> 4) * 4 + r;
+        if (ncol < N) out[(long)krow * N + ncol] = acc[nf][kf][r];
+      }
+    }
+  }
+}
+
+template __global__ void gemm_tn_partial3_map_kernel<0>(const bf16_t*, const bf16_t*, const bf16_t*, const bool*, float*, float*, int, int, int, int, int, const int*, int);
+template __global__ void gemm_tn_partial3_map_kernel<1>(const bf16_t*, const bf16_t*, const bf16_t*, const bool*, float*, float*, int, int, int, int, int, const int*, int);
+template __global__ void gemm_tn_partial3_map_kernel<2>(const bf16_t*, const bf16_t*, const bf16_t*, const bool*, float*, float*, int, int, int, int, int, const int*, int);
 
 // ---------------------------------------------------------------------------
 // dW^T orientation at 128x128 block / 64x64 wave tile: same vector-only

@@ -164,6 +164,56 @@ def bench_grouped(M, gated, iters=50):
           flush=True)
 
 
+def bench_tn_map(M, K, N, actin, density, iters=40):
+    """Device time (us) of one dW call (partial + reduce) through a row map of
+    M entries with about density * M live rows, compact operands, half gate."""
+    g = torch.Generator().manual_seed(M + K + N)
+    live = torch.rand(M, generator=g) < density
+    count = int(live.sum())
+    inv = torch.full((M,), -1, dtype=torch.int32)
+    inv[live] = torch.arange(count, dtype=torch.int32)
+    inv = inv.cuda()
+    cap = max(count, 1)
+    x = torch.randn(cap, K, device="cuda").to(torch.bfloat16)
+    dy = torch.randn(cap, N, device="cuda").to(torch.bfloat16)
+    y = torch.randn(cap, N, device="cuda").relu().to(torch.bfloat16)
+    gate = torch.rand(cap, device="cuda") < 0.5
+    dw = torch.zeros(K, N, device="cuda")
+    db = torch.zeros(N, device="cuda")
+    return _event_us(lambda: _C.gemm_tn_acc(x, dy, y if actin else dy, actin, dw, db, gate, None,
+                                            inv), iters)
+
+
+def bench_row_map(density):
+    """The six edge-level dW shapes through a row map: this process's kernel
+    (tn3map by default) against gemm_tn_partial3_kernel's map path, which a
+    child process with GCBF_NO_TN_SPARSE=1 times (the toggle is read once)."""
+    import json
+    import subprocess
+    child = os.environ.get("GEMM_BENCH_ROW_MAP_CHILD") == "1"
+    res = {}
+    for M in (167936, 83968):
+        for K, N, actin in TN_SHAPES:
+            res[f"{M},{K},{N},{actin}"] = bench_tn_map(M, K, N, actin, density)
+    if child:
+        print("ROWMAP " + json.dumps(res), flush=True)
+        return
+    env = dict(os.environ, GCBF_NO_TN_SPARSE="1", GEMM_BENCH_ROW_MAP_CHILD="1")
+    out = subprocess.run([sys.executable, os.path.abspath(__file__), "--row-map", str(density)],
+                         env=env, check=True, capture_output=True, text=True).stdout
+    old = json.loads([l for l in out.splitlines() if l.startswith("ROWMAP ")][-1][7:])
+    tot_new = tot_old = 0.0
+    for key, us in res.items():
+        M, K, N, actin = (int(v) for v in key.split(","))
+        print(f"TN row-map d={density} M={M:6d} K={K:3d} N={N:3d} actin={actin}: "
+              f"{_C.gemm_tn_map_path(M, K, N, actin, True).split()[0]} {us:6.1f} us | "
+              f"GCBF_NO_TN_SPARSE=1 {old[key]:6.1f} us  x{old[key] / us:4.2f}", flush=True)
+        tot_new += us
+        tot_old += old[key]
+    print(f"TN row-map d={density} sum of 12: {tot_new:7.1f} us | {tot_old:7.1f} us  "
+          f"x{tot_old / tot_new:4.2f}")
+
+
 def _parse_shapes(args):
     return [tuple(int(v) for v in a.split(",")) for a in args]
 
@@ -180,6 +230,11 @@ if __name__ == "__main__":
         for M in (4096, 2048):
             for gated in (False, True):
                 bench_grouped(M, gated)
+        sys.exit(0)
+    # `--row-map DENSITY`: dW through a row map per layer shape, new kernel
+    # against the GCBF_NO_TN_SPARSE=1 arm
+    if len(sys.argv) > 2 and sys.argv[1] == "--row-map":
+        bench_row_map(float(sys.argv[2]))
         sys.exit(0)
     for shape in [(167936, 256, 256), (167936, 32, 256), (167936, 256, 128),
                   (167936, 128, 128), (4096, 256, 256), (4096, 128, 256)]:
