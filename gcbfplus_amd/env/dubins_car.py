@@ -143,6 +143,26 @@ class DubinsCar(DoubleIntegrator):
     def forward_graph(self, graph: GraphBatch, action: Tensor) -> GraphBatch:
         return graph.with_agent_states(self._step_states(graph, action))
 
+    def loss_prep(self, graph: GraphBatch, raw: Tensor):
+        """Fused GCBF+ loss prologue: PID u_ref -> action = 2*raw + u_ref
+        (unclamped, as the eager branch of ``_loss`` takes the action loss)
+        -> stop freeze + euler of the clamped action -> [states;
+        next_states], differentiable w.r.t. ``raw``. Only for the exact class
+        on the GPU with the extension; ``None`` sends ``_loss`` down its
+        eager branch. GCBF_NO_FUSED_PREP forces that branch."""
+        from .. import ops
+
+        if (type(self) is not DubinsCar or not graph.states.is_cuda
+                or os.environ.get("GCBF_NO_FUSED_PREP") or not ops.hip_available()):
+            return None
+        if not hasattr(self, "_prep_lims"):
+            self._prep_lims = tuple(tuple(t.tolist() for t in lim)
+                                    for lim in (self.action_lim(), self.state_lim()))
+        p = self._params
+        return ops.dubins_loss_prep(graph.states, raw, self.num_agents, self._dt,
+                                    p["comm_radius"], 0.5 * p["car_radius"],
+                                    self.enable_stop, *self._prep_lims)
+
     def control_affine_dyn(self, state: Tensor) -> Tuple[Tensor, Tensor]:
         """(:249-259): f = [v cos, v sin, 0, 0]; g = [[0,0],[0,0],[10,0],[0,1]]."""
         th, v = state[..., 2], state[..., 3]

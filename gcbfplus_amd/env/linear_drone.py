@@ -120,6 +120,24 @@ class LinearDrone(DoubleIntegrator):
         return agent_states @ self._A_t.to(agent_states.device).t() + \
             action @ self._B_t.to(agent_states.device).t()
 
+    def loss_prep(self, graph: GraphBatch, raw: Tensor):
+        """Fused GCBF+ loss prologue: clipped-error LQR u_ref -> action =
+        2*raw + u_ref (unclamped, as the eager branch of ``_loss`` takes the
+        action loss) -> euler of A x + B clamp(action) -> [states;
+        next_states], differentiable w.r.t. ``raw``. Only for the exact class
+        on the GPU with the extension; ``None`` sends ``_loss`` down its
+        eager branch. GCBF_NO_FUSED_PREP forces that branch."""
+        if (type(self) is not LinearDrone or not graph.states.is_cuda
+                or os.environ.get("GCBF_NO_FUSED_PREP") or not ops.hip_available()):
+            return None
+        if not hasattr(self, "_prep_lims"):
+            self._prep_lims = tuple(tuple(t.tolist() for t in lim)
+                                    for lim in (self.action_lim(), self.state_lim()))
+        dev = graph.device
+        return ops.drone_loss_prep(graph.states, raw, self._K.to(dev), self._A_t.to(dev),
+                                   self._B_t.to(dev), self.num_agents, self._dt,
+                                   self._params["comm_radius"], *self._prep_lims)
+
     def control_affine_dyn(self, state: Tensor) -> Tuple[Tensor, Tensor]:
         f = state @ self._A_t.to(state.device).t()
         g = self._B_t.to(state.device).expand(*state.shape[:-1], 6, 3)

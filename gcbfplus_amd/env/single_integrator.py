@@ -4,6 +4,7 @@ edge_dim 2. BASELINE config #1 (CPU plumbing)."""
 from __future__ import annotations
 
 import math
+import os
 from typing import Optional, Tuple
 
 import numpy as np
@@ -75,6 +76,24 @@ class SingleIntegrator(DoubleIntegrator):
 
     def agent_xdot(self, agent_states: Tensor, action: Tensor) -> Tensor:
         return action
+
+    def loss_prep(self, graph: GraphBatch, raw: Tensor):
+        """Fused GCBF+ loss prologue: clipped-error LQR u_ref -> action =
+        2*raw + u_ref (unclamped, as the eager branch of ``_loss`` takes the
+        action loss) -> next = x + clamp(action) * dt -> [states;
+        next_states], differentiable w.r.t. ``raw``. Only for the exact class
+        on the GPU with the extension; ``None`` sends ``_loss`` down its
+        eager branch. GCBF_NO_FUSED_PREP forces that branch."""
+        from .. import ops
+
+        if (type(self) is not SingleIntegrator or not graph.states.is_cuda
+                or os.environ.get("GCBF_NO_FUSED_PREP") or not ops.hip_available()):
+            return None
+        if not hasattr(self, "_prep_lims"):
+            self._prep_lims = tuple(tuple(t.tolist() for t in lim)
+                                    for lim in (self.action_lim(), self.state_lim()))
+        return ops.si_loss_prep(graph.states, raw, self._K.to(graph.device), self.num_agents,
+                                self._dt, self._params["comm_radius"], *self._prep_lims)
 
     def control_affine_dyn(self, state: Tensor) -> Tuple[Tensor, Tensor]:
         f = torch.zeros_like(state)

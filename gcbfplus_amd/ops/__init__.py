@@ -31,6 +31,11 @@ Op inventory (kernel numbering follows SURVEY.md §2.7):
   di_loss_prep        K10 prologue: u_ref + action clamp + euler + [cur; next]
   crazyflie_loss_prep K10 prologue (CrazyFlie): u_ref + unclamped action + RK4 with
                       the low-level LQR + [cur; next]; dual-number backward
+  dubins_loss_prep    K10 prologue (DubinsCar): PID u_ref + unclamped action + stop
+                      freeze + euler + [cur; next]
+  drone_loss_prep     K10 prologue (LinearDrone): clipped-error LQR u_ref + unclamped
+                      action + euler of A x + B a + [cur; next]
+  si_loss_prep        K10 prologue (SingleIntegrator): same with xdot = a, no state clip
   proxqp_solve        K11: batched dense QP (labels; no grad)
   (env_step.hip K5-K8 is launched via env._step_fused: di_env_step for
   DoubleIntegrator/DubinsCar, drone3d_step and crazyflie_step as part A with
@@ -896,3 +901,78 @@ def crazyflie_loss_prep(states: Tensor, raw: Tensor, consts: Tensor, n_agents: i
     if not states.is_cuda:
         raise NotImplementedError("CPU path goes through env.u_ref / env.forward_graph")
     return _CrazyFlieLossPrepHIP.apply(states, raw, consts, n_agents)
+
+
+# --------------------------------------------------------------------------
+# fused GCBF+ minibatch prologue for DubinsCar, LinearDrone, SingleIntegrator
+# (env_loss_prep_{fwd,bwd}_kernel over the env structs of loss_prep_envs.h)
+# --------------------------------------------------------------------------
+class _EnvLossPrepHIP(torch.autograd.Function):
+    """u_ref -> action = 2*raw + u_ref (UNCLAMPED, as the action loss takes
+    it) -> next = clip_state(step(x, clamp(action))) -> big = [states;
+    next_states]: one kernel each way instead of a few dozen eager launches.
+    ``kind`` names the entry-point pair, ``mats`` the tensors it takes after
+    ``states`` (gain, A, B), ``tail`` its trailing scalars and limits.
+    Gradient flows to ``raw`` only (minibatch states are leaves)."""
+
+    @staticmethod
+    def forward(ctx, kind, states, raw, mats, n_agents, tail):
+        ext = _require_ext()
+        states, raw = states.contiguous(), raw.contiguous()
+        mats = tuple(m.contiguous() for m in mats)
+        action, big = getattr(ext, kind + "_loss_prep_fwd")(states, raw, *mats, n_agents, *tail)
+        # the unclamped action carries u_ref and the action clamp mask: raw is not kept
+        ctx.save_for_backward(states, action, *mats)
+        ctx.meta = (kind, n_agents, tail)
+        return action, big
+
+    @staticmethod
+    def backward(ctx, daction, dbig):
+        ext = _require_ext()
+        states, action, *mats = ctx.saved_tensors
+        kind, n_agents, tail = ctx.meta
+        if daction is None:
+            daction = torch.zeros_like(action)
+        if dbig is None:
+            B, V, S = states.shape
+            dbig = states.new_zeros(2 * B, V, S)
+        draw = getattr(ext, kind + "_loss_prep_bwd")(
+            states, *mats, action, daction.contiguous(), dbig.contiguous(), n_agents, *tail)
+        return None, None, draw, None, None, None
+
+
+def _lims(act_lim, state_lim):
+    return tuple([float(v) for v in lim] for lim in (*act_lim, *state_lim))
+
+
+def dubins_loss_prep(states: Tensor, raw: Tensor, n_agents: int, dt: float, comm: float,
+                     stop_r: float, enable_stop: bool, act_lim, state_lim):
+    """Returns (action (B,N,2) = 2*raw + u_ref unclamped, big_states (2B,V,4)
+    = [states; next_states]) for DubinsCar. states (B,V,4) with agent rows
+    [:N] and goal rows [N:2N]; act_lim / state_lim are (lo, hi) sequences of
+    floats (env.action_lim() / env.state_lim()), stop_r = 0.5 * car_radius.
+    GPU only (HIP, capture-safe); CPU callers take the composed env path."""
+    if not states.is_cuda:
+        raise NotImplementedError("CPU path goes through env.u_ref / env.forward_graph")
+    tail = (float(dt), float(comm), float(stop_r), bool(enable_stop), *_lims(act_lim, state_lim))
+    return _EnvLossPrepHIP.apply("dubins", states, raw, (), n_agents, tail)
+
+
+def drone_loss_prep(states: Tensor, raw: Tensor, K: Tensor, A: Tensor, Bm: Tensor,
+                    n_agents: int, dt: float, comm: float, act_lim, state_lim):
+    """LinearDrone: (action (B,N,3) unclamped, big_states (2B,V,6)). K (3,6)
+    LQR gain, A (6,6) and Bm (6,3) of xdot = A x + B a. GPU only."""
+    if not states.is_cuda:
+        raise NotImplementedError("CPU path goes through env.u_ref / env.forward_graph")
+    tail = (float(dt), float(comm), *_lims(act_lim, state_lim))
+    return _EnvLossPrepHIP.apply("drone", states, raw, (K, A, Bm), n_agents, tail)
+
+
+def si_loss_prep(states: Tensor, raw: Tensor, K: Tensor, n_agents: int, dt: float,
+                 comm: float, act_lim, state_lim):
+    """SingleIntegrator: (action (B,N,2) unclamped, big_states (2B,V,2)). K
+    (2,2) LQR gain; state_lim is all infinite (no state clip). GPU only."""
+    if not states.is_cuda:
+        raise NotImplementedError("CPU path goes through env.u_ref / env.forward_graph")
+    tail = (float(dt), float(comm), *_lims(act_lim, state_lim))
+    return _EnvLossPrepHIP.apply("si", states, raw, (K,), n_agents, tail)

@@ -11,6 +11,7 @@
 
 #include "crazyflie_consts.h"
 #include "dw_group.h"
+#include "loss_prep_envs.h"  // PrepArgs, the env structs, env_loss_prep_*_kernel decls
 
 // kernel decls (defined in the .hip TUs)
 typedef __bf16 bf16_t_;
@@ -1768,7 +1769,214 @@ torch::Tensor crazyflie_loss_prep_bwd(torch::Tensor states, torch::Tensor consts
   return draw;
 }
 
+// DubinsCar / LinearDrone / SingleIntegrator loss prologue (env struct E of
+// loss_prep_envs.h). Every check runs before the launch.
+static void env_prep_check_f32(const torch::Tensor& t, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.scalar_type() == torch::kFloat32 &&
+                  reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,
+              name, " must be a contiguous, 16-byte aligned float32 GPU tensor");
+}
+
+static void env_prep_check_mat(const torch::Tensor& t, const char* name,
+                               const torch::Tensor& states, long r, long c) {
+  env_prep_check_f32(t, name);
+  TORCH_CHECK(t.dim() == 2 && t.size(0) == r && t.size(1) == c, name, " must be (", r, ", ", c,
+              ")");
+  TORCH_CHECK(t.device() == states.device(), name, " must be on the device of states");
+}
+
+template <class E>
+static void env_prep_check_bnu(const torch::Tensor& t, const char* name,
+                               const torch::Tensor& states, long N) {
+  env_prep_check_f32(t, name);
+  TORCH_CHECK(t.dim() == 3 && t.size(0) == states.size(0) && t.size(1) == N &&
+                  t.size(2) == E::NU,
+              name, " must be (B, N, ", (int)E::NU, ")");
+  TORCH_CHECK(t.device() == states.device(), name, " must be on the device of states");
+}
+
+// states (B, V, S) with N agent and N goal rows, the limits, dt and comm
+template <class E>
+static typename E::Args env_prep_args(const torch::Tensor& states, long N, double dt,
+                                      double comm, const std::vector<double>& act_lo,
+                                      const std::vector<double>& act_hi,
+                                      const std::vector<double>& st_lo,
+                                      const std::vector<double>& st_hi) {
+  env_prep_check_f32(states, "states");
+  TORCH_CHECK(states.dim() == 3 && states.size(2) == E::S, "states must be (B, V, ", (int)E::S,
+              ")");
+  TORCH_CHECK(N > 0 && states.size(1) >= 2 * N, "states must hold N agent and N goal rows");
+  TORCH_CHECK(states.size(0) <= INT_MAX / 2 && states.size(1) <= INT_MAX,
+              "states batch too large");
+  TORCH_CHECK((long)act_lo.size() == E::NU && (long)act_hi.size() == E::NU,
+              "action limits must hold ", (int)E::NU, " values each");
+  TORCH_CHECK((long)st_lo.size() == E::S && (long)st_hi.size() == E::S,
+              "state limits must hold ", (int)E::S, " values each");
+  typename E::Args p;
+  for (int c = 0; c < E::NU; ++c) p.alo[c] = (float)act_lo[c], p.ahi[c] = (float)act_hi[c];
+  for (int s = 0; s < E::S; ++s) p.slo[s] = (float)st_lo[s], p.shi[s] = (float)st_hi[s];
+  p.dt = (float)dt;
+  p.comm = (float)comm;
+  p.stop_r = -1.f;
+  p.K = p.A = p.Bm = nullptr;
+  return p;
+}
+
+template <class E>
+static std::vector<torch::Tensor> env_loss_prep_fwd(const torch::Tensor& states,
+                                                    const torch::Tensor& raw, long N,
+                                                    const typename E::Args& p) {
+  env_prep_check_bnu<E>(raw, "raw", states, N);
+  long B = states.size(0), V = states.size(1);
+  torch::Tensor action = torch::empty({B, N, E::NU}, states.options());
+  torch::Tensor big = torch::empty({2 * B, V, E::S}, states.options());
+  long rows = 2 * B * V;
+  if (rows == 0) return {action, big};
+  // two trips of the grid-stride loop per thread: most rows are 8- to 24-byte
+  // copies, and half the blocks move them just as well
+  hipLaunchKernelGGL(env_loss_prep_fwd_kernel<E>, dim3((rows + 511) / 512), dim3(256), 0,
+                     cur_stream(), states.data_ptr<float>(), raw.data_ptr<float>(),
+                     action.data_ptr<float>(), big.data_ptr<float>(), (int)B, (int)V, (int)N,
+                     p);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return {action, big};
+}
+
+template <class E>
+static torch::Tensor env_loss_prep_bwd(const torch::Tensor& states, const torch::Tensor& action,
+                                       const torch::Tensor& daction, const torch::Tensor& dbig,
+                                       long N, const typename E::Args& p) {
+  env_prep_check_bnu<E>(action, "action", states, N);
+  env_prep_check_bnu<E>(daction, "daction", states, N);
+  env_prep_check_f32(dbig, "dbig");
+  long B = states.size(0), V = states.size(1);
+  TORCH_CHECK(dbig.dim() == 3 && dbig.size(0) == 2 * B && dbig.size(1) == V &&
+                  dbig.size(2) == E::S && dbig.device() == states.device(),
+              "dbig must be (2B, V, ", (int)E::S, ") on the device of states");
+  auto draw = torch::empty_like(action);
+  long total = B * N;
+  if (total == 0) return draw;
+  hipLaunchKernelGGL(env_loss_prep_bwd_kernel<E>, dim3((total + 255) / 256), dim3(256), 0,
+                     cur_stream(), states.data_ptr<float>(), action.data_ptr<float>(),
+                     daction.data_ptr<float>(), dbig.data_ptr<float>(),
+                     draw.data_ptr<float>(), (int)B, (int)V, (int)N, p);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return draw;
+}
+
+typedef std::vector<double> Lim;
+
+static DubinsPrep::Args dubins_prep_args(const torch::Tensor& states, long N, double dt,
+                                         double comm, double stop_r, bool enable_stop,
+                                         const Lim& alo, const Lim& ahi, const Lim& slo,
+                                         const Lim& shi) {
+  auto p = env_prep_args<DubinsPrep>(states, N, dt, comm, alo, ahi, slo, shi);
+  TORCH_CHECK(stop_r >= 0, "stop_r must not be negative");
+  p.stop_r = enable_stop ? (float)stop_r : -1.f;
+  return p;
+}
+
+std::vector<torch::Tensor> dubins_loss_prep_fwd(torch::Tensor states, torch::Tensor raw, long N,
+                                                double dt, double comm, double stop_r,
+                                                bool enable_stop, Lim alo, Lim ahi, Lim slo,
+                                                Lim shi) {
+  auto p = dubins_prep_args(states, N, dt, comm, stop_r, enable_stop, alo, ahi, slo, shi);
+  return env_loss_prep_fwd<DubinsPrep>(states, raw, N, p);
+}
+
+torch::Tensor dubins_loss_prep_bwd(torch::Tensor states, torch::Tensor action,
+                                   torch::Tensor daction, torch::Tensor dbig, long N, double dt,
+                                   double comm, double stop_r, bool enable_stop, Lim alo,
+                                   Lim ahi, Lim slo, Lim shi) {
+  auto p = dubins_prep_args(states, N, dt, comm, stop_r, enable_stop, alo, ahi, slo, shi);
+  return env_loss_prep_bwd<DubinsPrep>(states, action, daction, dbig, N, p);
+}
+
+static DronePrep::Args drone_prep_args(const torch::Tensor& states, const torch::Tensor& Kmat,
+                                       const torch::Tensor& A, const torch::Tensor& Bm, long N,
+                                       double dt, double comm, const Lim& alo, const Lim& ahi,
+                                       const Lim& slo, const Lim& shi) {
+  auto p = env_prep_args<DronePrep>(states, N, dt, comm, alo, ahi, slo, shi);
+  env_prep_check_mat(Kmat, "K", states, 3, 6);
+  env_prep_check_mat(A, "A", states, 6, 6);
+  env_prep_check_mat(Bm, "Bm", states, 6, 3);
+  p.K = Kmat.data_ptr<float>();
+  p.A = A.data_ptr<float>();
+  p.Bm = Bm.data_ptr<float>();
+  return p;
+}
+
+std::vector<torch::Tensor> drone_loss_prep_fwd(torch::Tensor states, torch::Tensor raw,
+                                               torch::Tensor Kmat, torch::Tensor A,
+                                               torch::Tensor Bm, long N, double dt, double comm,
+                                               Lim alo, Lim ahi, Lim slo, Lim shi) {
+  auto p = drone_prep_args(states, Kmat, A, Bm, N, dt, comm, alo, ahi, slo, shi);
+  return env_loss_prep_fwd<DronePrep>(states, raw, N, p);
+}
+
+torch::Tensor drone_loss_prep_bwd(torch::Tensor states, torch::Tensor Kmat, torch::Tensor A,
+                                  torch::Tensor Bm, torch::Tensor action, torch::Tensor daction,
+                                  torch::Tensor dbig, long N, double dt, double comm, Lim alo,
+                                  Lim ahi, Lim slo, Lim shi) {
+  auto p = drone_prep_args(states, Kmat, A, Bm, N, dt, comm, alo, ahi, slo, shi);
+  return env_loss_prep_bwd<DronePrep>(states, action, daction, dbig, N, p);
+}
+
+static SiPrep::Args si_prep_args(const torch::Tensor& states, const torch::Tensor& Kmat, long N,
+                                 double dt, double comm, const Lim& alo, const Lim& ahi,
+                                 const Lim& slo, const Lim& shi) {
+  auto p = env_prep_args<SiPrep>(states, N, dt, comm, alo, ahi, slo, shi);
+  env_prep_check_mat(Kmat, "K", states, 2, 2);
+  p.K = Kmat.data_ptr<float>();
+  return p;
+}
+
+std::vector<torch::Tensor> si_loss_prep_fwd(torch::Tensor states, torch::Tensor raw,
+                                            torch::Tensor Kmat, long N, double dt, double comm,
+                                            Lim alo, Lim ahi, Lim slo, Lim shi) {
+  auto p = si_prep_args(states, Kmat, N, dt, comm, alo, ahi, slo, shi);
+  return env_loss_prep_fwd<SiPrep>(states, raw, N, p);
+}
+
+torch::Tensor si_loss_prep_bwd(torch::Tensor states, torch::Tensor Kmat, torch::Tensor action,
+                               torch::Tensor daction, torch::Tensor dbig, long N, double dt,
+                               double comm, Lim alo, Lim ahi, Lim slo, Lim shi) {
+  auto p = si_prep_args(states, Kmat, N, dt, comm, alo, ahi, slo, shi);
+  return env_loss_prep_bwd<SiPrep>(states, action, daction, dbig, N, p);
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("dubins_loss_prep_fwd", &dubins_loss_prep_fwd,
+        "fused DubinsCar loss prologue: (action unclamped, [states; next_states])",
+        py::arg("states"), py::arg("raw"), py::arg("N"), py::arg("dt"), py::arg("comm"),
+        py::arg("stop_r"), py::arg("enable_stop"), py::arg("act_lo"), py::arg("act_hi"),
+        py::arg("st_lo"), py::arg("st_hi"));
+  m.def("dubins_loss_prep_bwd", &dubins_loss_prep_bwd,
+        "gradient of the DubinsCar loss prologue w.r.t. raw",
+        py::arg("states"), py::arg("action"), py::arg("daction"), py::arg("dbig"),
+        py::arg("N"), py::arg("dt"), py::arg("comm"), py::arg("stop_r"),
+        py::arg("enable_stop"), py::arg("act_lo"), py::arg("act_hi"), py::arg("st_lo"),
+        py::arg("st_hi"));
+  m.def("drone_loss_prep_fwd", &drone_loss_prep_fwd,
+        "fused LinearDrone loss prologue: (action unclamped, [states; next_states])",
+        py::arg("states"), py::arg("raw"), py::arg("K"), py::arg("A"), py::arg("Bm"),
+        py::arg("N"), py::arg("dt"), py::arg("comm"), py::arg("act_lo"), py::arg("act_hi"),
+        py::arg("st_lo"), py::arg("st_hi"));
+  m.def("drone_loss_prep_bwd", &drone_loss_prep_bwd,
+        "gradient of the LinearDrone loss prologue w.r.t. raw",
+        py::arg("states"), py::arg("K"), py::arg("A"), py::arg("Bm"), py::arg("action"),
+        py::arg("daction"), py::arg("dbig"), py::arg("N"), py::arg("dt"), py::arg("comm"),
+        py::arg("act_lo"), py::arg("act_hi"), py::arg("st_lo"), py::arg("st_hi"));
+  m.def("si_loss_prep_fwd", &si_loss_prep_fwd,
+        "fused SingleIntegrator loss prologue: (action unclamped, [states; next_states])",
+        py::arg("states"), py::arg("raw"), py::arg("K"), py::arg("N"), py::arg("dt"),
+        py::arg("comm"), py::arg("act_lo"), py::arg("act_hi"), py::arg("st_lo"),
+        py::arg("st_hi"));
+  m.def("si_loss_prep_bwd", &si_loss_prep_bwd,
+        "gradient of the SingleIntegrator loss prologue w.r.t. raw",
+        py::arg("states"), py::arg("K"), py::arg("action"), py::arg("daction"),
+        py::arg("dbig"), py::arg("N"), py::arg("dt"), py::arg("comm"), py::arg("act_lo"),
+        py::arg("act_hi"), py::arg("st_lo"), py::arg("st_hi"));
   m.def("di_loss_prep_fwd", &di_loss_prep_fwd);
   m.def("di_loss_prep_bwd", &di_loss_prep_bwd);
   m.def("crazyflie_loss_prep_fwd", &crazyflie_loss_prep_fwd,

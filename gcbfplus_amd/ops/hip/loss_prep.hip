@@ -233,3 +233,140 @@ void crazyflie_loss_prep_bwd_kernel(const float* __restrict__ states,   // (B,V,
     draw[it] = two_da + 2.f * acc;
   }
 }
+
+// ---------------------------------------------------------------------------
+// DubinsCar / LinearDrone / SingleIntegrator prologue: one templated kernel
+// pair over the per-env structs of loss_prep_envs.h (u_ref, step, jacobian in
+// one place per env). Same contract as the CrazyFlie prologue above: action
+// stored unclamped, dynamics on the clamped action, gradient to raw only.
+// ---------------------------------------------------------------------------
+#include "loss_prep_envs.h"
+
+// Row moves use the widest vector the row stride keeps aligned on a 16-byte
+// aligned base: 16 B for W % 4 == 0, 8 B for even W (24-byte S = 6 rows are
+// only 8-byte aligned), scalars otherwise (NU = 3).
+template <int W>
+__device__ __forceinline__ void load_vec(const float* __restrict__ p, float* r) {
+  if constexpr (W % 4 == 0) {
+#pragma unroll
+    for (int k = 0; k < W / 4; ++k) {
+      const float4 t = ((const float4*)p)[k];
+      r[4 * k] = t.x, r[4 * k + 1] = t.y, r[4 * k + 2] = t.z, r[4 * k + 3] = t.w;
+    }
+  } else if constexpr (W % 2 == 0) {
+#pragma unroll
+    for (int k = 0; k < W / 2; ++k) {
+      const float2 t = ((const float2*)p)[k];
+      r[2 * k] = t.x, r[2 * k + 1] = t.y;
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < W; ++k) r[k] = p[k];
+  }
+}
+
+template <int W>
+__device__ __forceinline__ void store_vec(float* __restrict__ p, const float* r) {
+  if constexpr (W % 4 == 0) {
+#pragma unroll
+    for (int k = 0; k < W / 4; ++k)
+      ((float4*)p)[k] = make_float4(r[4 * k], r[4 * k + 1], r[4 * k + 2], r[4 * k + 3]);
+  } else if constexpr (W % 2 == 0) {
+#pragma unroll
+    for (int k = 0; k < W / 2; ++k) ((float2*)p)[k] = make_float2(r[2 * k], r[2 * k + 1]);
+  } else {
+#pragma unroll
+    for (int k = 0; k < W; ++k) p[k] = r[k];
+  }
+}
+
+template <class E>
+__launch_bounds__(256) __global__
+void env_loss_prep_fwd_kernel(const float* __restrict__ states, const float* __restrict__ raw,
+                              float* __restrict__ action, float* __restrict__ big,
+                              int B, int V, int N, const typename E::Args p) {
+  constexpr int S = E::S, NU = E::NU;
+  const long rows = (long)2 * B * V;
+  for (long row = (long)blockIdx.x * blockDim.x + threadIdx.x; row < rows;
+       row += (long)gridDim.x * blockDim.x) {
+    const int v = row % V;
+    const long bb = row / V;
+    const int half = bb / B;     // 0: current, 1: next
+    const long b = bb % B;
+    float x[S];
+    load_vec<S>(states + (b * V + v) * S, x);
+    float* dst = big + row * S;
+    if (half == 0 || v >= N) {
+      store_vec<S>(dst, x);
+      continue;
+    }
+    // next agent state for agent i = v
+    const long ag = b * N + v;
+    float g[S], r[NU], u[NU], act[NU], ac[NU], pre[S];
+    load_vec<S>(states + (b * V + N + v) * S, g);
+    load_vec<NU>(raw + ag * NU, r);
+    E::uref(x, g, p, u);
+#pragma unroll
+    for (int c = 0; c < NU; ++c) {
+      act[c] = 2.f * r[c] + u[c];
+      ac[c] = fminf(fmaxf(act[c], p.alo[c]), p.ahi[c]);
+    }
+    store_vec<NU>(action + ag * NU, act);
+    E::step(x, g, ac, p, pre);
+#pragma unroll
+    for (int s = 0; s < S; ++s) pre[s] = fminf(fmaxf(pre[s], p.slo[s]), p.shi[s]);
+    store_vec<S>(dst, pre);
+  }
+}
+
+// one thread per (b, agent); no atomics, every draw element written once
+template <class E>
+__launch_bounds__(256) __global__
+void env_loss_prep_bwd_kernel(const float* __restrict__ states,
+                              const float* __restrict__ action,
+                              const float* __restrict__ daction,
+                              const float* __restrict__ dbig, float* __restrict__ draw,
+                              int B, int V, int N, const typename E::Args p) {
+  constexpr int S = E::S, NU = E::NU;
+  const long total = (long)B * N;
+  for (long ag = (long)blockIdx.x * blockDim.x + threadIdx.x; ag < total;
+       ag += (long)gridDim.x * blockDim.x) {
+    const int i = ag % N;
+    const long b = ag / N;
+    float x[S], g[S], act[NU], ac[NU], da[NU], dn[S], pre[S], J[S][NU], out[NU];
+    load_vec<S>(states + (b * V + i) * S, x);
+    load_vec<S>(states + (b * V + N + i) * S, g);
+    load_vec<NU>(action + ag * NU, act);
+    load_vec<NU>(daction + ag * NU, da);
+    load_vec<S>(dbig + ((B + b) * V + i) * S, dn);
+#pragma unroll
+    for (int c = 0; c < NU; ++c) ac[c] = fminf(fmaxf(act[c], p.alo[c]), p.ahi[c]);
+    // the pre-clip next state again: clip_state's mask
+    E::step(x, g, ac, p, pre);
+    E::jac(x, g, p, J);
+#pragma unroll
+    for (int c = 0; c < NU; ++c) {
+      float acc = 0.f;
+#pragma unroll
+      for (int s = 0; s < S; ++s) {
+        const bool pass = pre[s] >= p.slo[s] && pre[s] <= p.shi[s] && J[s][c] != 0.f;
+        acc += pass ? dn[s] * J[s][c] : 0.f;
+      }
+      const float two_da = 2.f * da[c];
+      // clamp active: nothing flows from the dynamics
+      out[c] = (act[c] >= p.alo[c] && act[c] <= p.ahi[c]) ? two_da + 2.f * acc : two_da;
+    }
+    store_vec<NU>(draw + ag * NU, out);
+  }
+}
+
+#define INSTANTIATE_ENV_LOSS_PREP(E)                                                       \
+  template __global__ void env_loss_prep_fwd_kernel<E>(const float*, const float*, float*, \
+                                                       float*, int, int, int,              \
+                                                       const E::Args);                     \
+  template __global__ void env_loss_prep_bwd_kernel<E>(const float*, const float*,         \
+                                                       const float*, const float*, float*, \
+                                                       int, int, int, const E::Args);
+INSTANTIATE_ENV_LOSS_PREP(SiPrep)
+INSTANTIATE_ENV_LOSS_PREP(DronePrep)
+INSTANTIATE_ENV_LOSS_PREP(DubinsPrep)

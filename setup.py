@@ -30,8 +30,10 @@ setup(
             ],
             # headers: crazyflie_dyn.h is shared by env_step.hip and loss_prep.hip,
             # crazyflie_edge.h by the mode-2 and jacobian kernels of edge_msg.hip,
-            # dw_group.h (grouped dW problem tables) by gemm.hip and bindings.hip
+            # dw_group.h (grouped dW problem tables) by gemm.hip and bindings.hip,
+            # loss_prep_envs.h (per-env prologue math) by loss_prep.hip and bindings.hip
             depends=[
+                "gcbfplus_amd/ops/hip/loss_prep_envs.h",
                 "gcbfplus_amd/ops/hip/common.h",
                 "gcbfplus_amd/ops/hip/dw_group.h",
                 "gcbfplus_amd/ops/hip/crazyflie_consts.h",
